@@ -8,7 +8,12 @@ rank at N>1 = configs[4]'s global 8192 on 8 GPUs). Consecutive batches are pipel
 (engine.FusedPipeline): batch i's fusion and gather overlap batch i+1's encoders; the timed
 region ends after the last batch's gather (device synchronize).
 
-The path runs at three precisions on the same inputs; rank 0 prints ONE JSON line:
+A plain run sets up, warms up, times K steps of the headline precision, writes that path's
+outputs of the last timed step if --dump-outputs DIR is given, and prints the result line; the
+nested precisions, `parity`, `cpu_baseline`, `per_config` and the isolated FFN1 figures below are
+measured with --full only.
+
+With --full the path runs at three precisions on the same inputs; rank 0 prints ONE JSON line:
   headline  "fp32x3": the reference's fp32 arithmetic (inference/text_inference.py:91-93,
             inference/image_inference.py:116-118) with every GEMM / conv operand carried as a
             pair of f16 planes (hi + lo: 22 significant bits; activations at a per-tensor
@@ -33,6 +38,7 @@ At N>1 rank 0 also checks two gathered rows of EVERY rank against the oracle run
 inputs (the all-gather's order and content).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--precision all|both|fp32x3|fp32|f16]
+                    [--full] [--dump-outputs DIR]
 
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py starts
 `python -m torch.distributed.run --nproc-per-node N ... bench.py` as a child process BEFORE any
@@ -121,7 +127,43 @@ def parse(argv=None):
     ap.add_argument('--stub', action='store_true',
                     help='CPU stub step over gloo (launcher / gather check; automatic with no GPU visible)')
     ap.add_argument('--json-out', default=None, help='also write the result line to this file (rank 0)')
+    ap.add_argument('--full', action='store_true',
+                    help='beside the headline: the other precisions of --precision (nested), the oracle parity '
+                         'check, the CPU baseline, the per-config timings and the isolated FFN1 roofline run')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help="write the headline path's outputs of the last timed step to DIR/<name>.npy (rank 0)")
     return ap.parse_args(argv)
+
+
+def headline_precision(name: str):
+    """(precisions a --full run times, in run order; the one whose line is the headline)."""
+    precs = {'all': ['f16', 'fp32x3', 'fp32'], 'both': ['f16', 'fp32']}.get(name, [name])
+    return precs, next(p for p in ('fp32x3', 'fp32', 'f16') if p in precs)
+
+
+DUMP_BYTES = 48 << 20  # --dump-outputs writes at most this much
+OUT_NAMES = {'speech': ('feat', 'logits', 'probs'), 'text': ('feat', 'logits', 'probs'),
+             'image': ('feat', 'logits', 'probs'),
+             'fusion': ('logits', 'probs', 'attention_weights', 'decision_weights')}
+
+
+def dump_outputs(dirname: str, out, rows) -> None:
+    """--dump-outputs: what one step of the timed path hands its caller -- FusedPipeline.forward's
+    per-modality (feat, logits, probs) and fusion (logits, probs, attention, decision weights), and the
+    epilogue's packed (at N > 1: gathered) 34-float result rows -- as float32 DIR/<name>.npy. Beyond
+    DUMP_BYTES in all (batches far above the default ones) every array keeps the same number of its
+    rows, a sorted sample seeded by the array's row count."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {f'{mod}_{n}': t for mod, names in OUT_NAMES.items() for n, t in zip(names, (out or {}).get(mod, ()))}
+    arrays['rows'] = rows
+    arrays = {k: (t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)) for k, t in arrays.items()}
+    keep = None
+    if sum(4 * v.size for v in arrays.values()) > DUMP_BYTES:
+        keep = max(1, DUMP_BYTES // sum(4 * v.size // len(v) for v in arrays.values()))
+    for name, arr in arrays.items():
+        if keep is not None and len(arr) > keep:
+            arr = arr[np.sort(np.random.default_rng(len(arr)).choice(len(arr), size=keep, replace=False))]
+        np.save(os.path.join(dirname, name + '.npy'), np.ascontiguousarray(arr, dtype=np.float32))
 
 
 # ----------------------------------------------------------------------------- launcher
@@ -408,9 +450,9 @@ def per_config(pipe, dev, precision, iters=10):
     return out
 
 
-def run(a, precision, B, world, rank, dev, inputs):
+def run(a, precision, B, world, rank, dev, inputs, dump=None):
     """Time K pipelined steps at one precision; returns (result line or None, last outputs,
-    gathered rows or None)."""
+    gathered rows or None). `dump`: directory for the last timed step's outputs (rank 0)."""
     from mec import _lib, dist as mdist, engine
     # the product library: no probe build (probe option values skip work and return wrong
     # results), and every knob of the pipeline's handles at its default (handles own their knobs)
@@ -462,12 +504,16 @@ def run(a, precision, B, world, rank, dev, inputs):
     pipe.check()  # an after-the-fact kernel error (mec_model_check) fails the run, never a silent NaN
     ffn_ms, ffn_n = pipe.text.prof_read()
     gather_ms = [e0.elapsed_time(e1) for e0, e1 in gather_ev]
-    # the same kernel with BERT alone on the GPU (no concurrent image stream), untimed region
-    pipe.text.prof_enable('bert_ffn1')
-    for _ in range(2):
-        pipe.text.forward(ids, mask)
-    torch.cuda.synchronize()
-    iso_ms, iso_n = pipe.text.prof_read()
+    if dump and rank == 0:
+        dump_outputs(dump, last.get('out'), last['rows'])
+    iso_ms, iso_n = 0.0, 0
+    if a.full:
+        # the same kernel with BERT alone on the GPU (no concurrent image stream), untimed region
+        pipe.text.prof_enable('bert_ffn1')
+        for _ in range(2):
+            pipe.text.forward(ids, mask)
+        torch.cuda.synchronize()
+        iso_ms, iso_n = pipe.text.prof_read()
     pipe.text.prof_enable(0)
     t = torch.tensor([el], device=dev, dtype=torch.float64)
     if world > 1:
@@ -517,7 +563,7 @@ def run(a, precision, B, world, rank, dev, inputs):
             # on the B [CLS] rows only, as an untagged launch of its own shape
             'launches_expected': 11 * a.steps,
             'note': 'achieved: live in the timed region (CUs shared with the image stream); '
-                    'achieved_isolated: BERT alone',
+                    'achieved_isolated: BERT alone (a run of its own: --full)',
             'achieved_isolated': iso, 'frac_isolated': (iso / peak) if iso else None}
     if precision == 'fp32x3' and achieved:
         # the same launch priced as fp32 work: algorithmic FLOPs / time, against the f32 MFMA peak
@@ -563,7 +609,7 @@ def run(a, precision, B, world, rank, dev, inputs):
                               'rccl_version': '.'.join(map(str, torch.cuda.nccl.version())),
                               'all_gather_ms_per_step': (sum(gather_ms) / len(gather_ms)) if gather_ms else None,
                               'all_gather_bytes_per_step': world * B * ROW * 4}
-    if world == 1 and not a.no_configs:
+    if world == 1 and a.full and not a.no_configs:
         res['per_config'] = per_config(pipe, dev, precision)
     out = last.get('out')
     return res, (out, pipe), gathered
@@ -579,19 +625,21 @@ def main_gpu(a, world, rank, local):
     B = a.batch or (256 if world == 1 else 1024)
     inputs = (syn.speech_inputs(B, seed=rank), *syn.text_inputs(B, 128, seed=rank, ragged=False),
               syn.image_inputs(B, seed=rank))
-    precs = {'all': ['f16', 'fp32x3', 'fp32'], 'both': ['f16', 'fp32']}.get(a.precision, [a.precision])
+    precs, hp = headline_precision(a.precision)
+    if not a.full:  # a plain run times the headline precision alone
+        precs = [hp]
     lines, outs, gathered = {}, {}, {}
     for p in precs:
-        res, o, gth = run(a, p, B, world, rank, dev, inputs)
+        res, o, gth = run(a, p, B, world, rank, dev, inputs, dump=a.dump_outputs if p == hp else None)
         lines[p], outs[p], gathered[p] = res, o, gth
     if rank == 0:
         rows = parity_rows(B, a.oracle_rows)
-        need_oracle = not a.no_parity or (world == 1 and not a.no_cpu_baseline)
-        ref, cb = (oracle_run(*inputs, rows, timed=(world == 1 and not a.no_cpu_baseline))
-                   if need_oracle else (None, None))
+        do_parity = a.full and not a.no_parity
+        do_cpu = a.full and world == 1 and not a.no_cpu_baseline
+        ref, cb = oracle_run(*inputs, rows, timed=do_cpu) if do_parity or do_cpu else (None, None)
         for p in precs:
             out, pipe = outs[p]
-            if not a.no_parity and out is not None:
+            if do_parity and out is not None:
                 lines[p]['parity'] = parity(out, ref, rows)
                 if world > 1:
                     lines[p]['parity']['all_gather_rows'] = gather_check(gathered[p], world, B)
@@ -599,7 +647,6 @@ def main_gpu(a, world, rank, local):
                 m.close()
             if cb is not None:
                 lines[p]['cpu_baseline'] = cb
-        hp = next(p for p in ('fp32x3', 'fp32', 'f16') if p in lines)
         head = lines[hp]
         for p, key in (('fp32', 'fp32_exact_path'), ('f16', 'f16_fast_path'), ('fp32x3', 'fp32x3_path')):
             if p != hp and p in lines:
@@ -660,6 +707,8 @@ def main_stub(a, world, rank):
                 'distributed': {'world_size': dist.get_world_size() if world > 1 else 1,
                                 'backend': dist.get_backend() if world > 1 else None,
                                 'gathered_rows_in_order': ok}}
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, None, rows)
         print(json.dumps(line), flush=True)
         if a.json_out:
             with open(a.json_out, 'w') as fh:

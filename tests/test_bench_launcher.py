@@ -42,6 +42,55 @@ def test_bench_single_rank_stub():
     assert r['n_gpus'] == 1 and r['distributed']['gathered_rows_in_order'] is True
 
 
+def test_bench_stub_dumps_the_gathered_rows(tmp_path):
+    """--dump-outputs DIR: the rows the last step produced, float32, a function of the arguments alone."""
+    sys.path.insert(0, ROOT)
+    import bench
+    r = _run_bench('--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '5', '--dump-outputs', str(tmp_path / 'a'))
+    assert r['steps'] == 2 and r['ms_per_step'] > 0
+    a = np.load(tmp_path / 'a' / 'rows.npy')
+    assert os.listdir(tmp_path / 'a') == ['rows.npy'] and a.dtype == np.float32 and a.shape == (10, bench.ROW)
+    assert np.array_equal(a, bench.stub_rows(0, 10).numpy())
+
+
+def test_dump_outputs_names_dtype_and_size_cap(tmp_path, monkeypatch):
+    sys.path.insert(0, ROOT)
+    import bench
+    import torch
+    B = 64
+    rng = np.random.default_rng(0)
+    out = {mod: tuple(torch.from_numpy(rng.standard_normal((B, 7 + i)).astype(np.float32)) for i in range(len(names)))
+           for mod, names in bench.OUT_NAMES.items()}
+    rows = torch.from_numpy(rng.standard_normal((2 * B, bench.ROW)))  # float64 in, gathered over 2 ranks
+    bench.dump_outputs(str(tmp_path / 'all'), out, rows)
+    want = {f'{m}_{n}.npy' for m, names in bench.OUT_NAMES.items() for n in names} | {'rows.npy'}
+    assert set(os.listdir(tmp_path / 'all')) == want
+    for f in want:
+        assert np.load(tmp_path / 'all' / f).dtype == np.float32
+    assert np.array_equal(np.load(tmp_path / 'all' / 'text_probs.npy'), out['text'][2].numpy())
+    assert np.array_equal(np.load(tmp_path / 'all' / 'rows.npy'), rows.numpy().astype(np.float32))
+    # over the cap: every array keeps the same seeded sample size of its rows, and the total fits
+    monkeypatch.setattr(bench, 'DUMP_BYTES', 4096)
+    for d in ('c1', 'c2'):
+        bench.dump_outputs(str(tmp_path / d), out, rows)
+    got = {f: np.load(tmp_path / 'c1' / f) for f in want}
+    assert sum(v.nbytes for v in got.values()) <= 4096 and len({len(v) for v in got.values()}) == 1
+    assert all(np.array_equal(v, np.load(tmp_path / 'c2' / f)) for f, v in got.items())
+    full = out['image'][0].numpy()
+    assert all(any(np.array_equal(r, f) for f in full) for r in got['image_feat.npy'])
+
+
+def test_plain_run_times_the_headline_precision_only():
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.headline_precision('all') == (['f16', 'fp32x3', 'fp32'], 'fp32x3')
+    assert bench.headline_precision('both') == (['f16', 'fp32'], 'fp32')
+    assert bench.headline_precision('f16') == (['f16'], 'f16')
+    a = bench.parse([])
+    assert a.full is False and a.dump_outputs is None
+    assert bench.parse(['--full', '--dump-outputs', 'd']).full is True
+
+
 def test_stub_rows_and_shards_tile_the_global_batch():
     sys.path.insert(0, ROOT)
     import bench

@@ -6,6 +6,7 @@ timeout -k 10 ${TEST_TIMEOUT:-900} python -m pytest tests -m gpu -q -x ${PYTEST_
 rc=$?
 tail -30 gpurun_out/pytest_gpu.log
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then echo "pytest rc=$rc (crash/timeout): stopping"; exit $rc; fi
+BENCH_ARGS="--full ${BENCH_ARGS}"  # every precision, with the oracle parity check and the CPU baseline
 timeout -k 10 ${BENCH_TIMEOUT:-600} python bench.py --steps ${STEPS:-5} --warmup ${WARMUP:-2} ${BENCH_ARGS} > gpurun_out/bench.log 2>&1
 brc=$?
 tail -5 gpurun_out/bench.log

@@ -29,7 +29,7 @@ for step in "$@"; do
       fi
       rc=$?; tail -3 gpurun_out/${TAG}_pytest_gpu.log; [ $rc -ne 0 ] && exit $rc ;;
     bench|bench:*)
-      X=""; [ "$step" != bench ] && X="${step#bench:}"
+      X="--full"; [ "$step" != bench ] && X="--full ${step#bench:}"
       timeout -k 10 600 python -u bench.py $X --json-out gpurun_out/${TAG}_bench.json > gpurun_out/${TAG}_bench.log 2>&1 \
         || { tail -5 gpurun_out/${TAG}_bench.log; exit 1; }
       python3 tools/summ_bench.py gpurun_out/${TAG}_bench.json || exit 1 ;;

@@ -9,6 +9,7 @@ rc=$?
 grep -E "passed|failed|error" gpurun_out/${TAG}_pytest_gpu.log | tail -3
 if [ $rc -ne 0 ]; then grep -E "FAILED|Error|error" gpurun_out/${TAG}_pytest_gpu.log | head -20; exit $rc; fi
 [ -n "$NO_BENCH" ] && exit 0
+BENCH_ARGS="--full ${BENCH_ARGS}"  # the nested f16 line printed below is measured with --full only
 timeout -k 10 ${BENCH_TIMEOUT:-600} python -u bench.py ${BENCH_ARGS} --json-out gpurun_out/${TAG}_bench.json \
   > gpurun_out/${TAG}_bench.log 2>&1
 brc=$?
