@@ -162,6 +162,49 @@ int mec_gemm_f32(const float* A, const float* B, const float* bias, const float*
 /* Implicit-GEMM conv on NHWC f32 (C % 32 == 0), same geometry as mec_conv_f16. */
 int mec_conv_f32(const float* x, const float* w, const float* bias, const float* R, float* y, int n, int H, int W,
                  int C, int Cout, int ks, int stride, int pad, int act, void* stream);
+/* Conv geometry (mec_conv_f16, mec_conv_f32, mec_gemm_ex): n >= 1, ks >= 1, stride >= 1, pad >= 0 and
+ * ks <= H + 2 pad, ks <= W + 2 pad (OH, OW >= 1); anything else returns -1 before any launch. */
+
+/* Descriptor form of the f16 / split-f16 GEMM engine: every operand view, residual form and output form
+ * the models launch, through the same dispatch (tile forcing with "gemm_bn" and the halo-kernel routing
+ * included). A zeroed descriptor with oscale = cscale = 1 is mec_gemm_f16 without bias or residual.
+ *   amode    MEC_A_PLAIN: A[M,K]. MEC_A_CONV: A = NHWC x[n,H,W,C], implicit im2col, K ordered (kh, kw, c),
+ *            B = w[N][ks][ks][C]. MEC_A_DUAL: [A | A2] along K = K1 + C, A[M,K1] and A2 = NHWC [n,H,W,C]
+ *            read at (oh stride, ow stride) (ks = 1, pad = 0): a bottleneck's conv3 + strided downsample.
+ *            Conv / dual: M = n OH OW and K come from the geometry; the descriptor's M and K are ignored.
+ *   a_lo, b_lo  both != 0: split operands, the lo planes that many elements after A (and after A2) / B.
+ *   oscale   multiplies the accumulator before the bias (a power of two; 1 = none).
+ *   R        residual [M,N]: f32 (r_is_f32), f16, or an f16 hi plane with its lo plane at R + r_lo
+ *            (split operands only). r_stats [M][2] = (mean, rstd) with r_gamma, r_beta [N]: the f32 R
+ *            enters as fma((R - mean) * rstd, gamma, beta) (a deferred LayerNorm).
+ *   C16, C32 outputs (either or both); c_lo != 0: C16 as planes hi = f16(v cscale), lo = f16(v cscale - hi)
+ *            at C16 + c_lo (C32 carries v).
+ *   act      0 none, 1 relu, 2 gelu (f16 path's rational form), 3 relu6, 4 exact-erf gelu, 5 branch-free erf gelu. */
+enum { MEC_A_PLAIN = 0, MEC_A_CONV = 1, MEC_A_DUAL = 2 };
+typedef struct mec_gemm_args {
+  int amode;
+  const void* A;
+  long long a_lo;
+  const void* A2;
+  int K1;
+  const void* B;
+  long long b_lo;
+  float oscale;
+  const float* bias;
+  const void* R;
+  int r_is_f32;
+  long long r_lo;
+  const float* r_stats;
+  const float* r_gamma;
+  const float* r_beta;
+  void* C16;
+  long long c_lo;
+  float cscale;
+  float* C32;
+  int M, N, K, act;
+  int n, H, W, C, ks, stride, pad;
+} mec_gemm_args;
+int mec_gemm_ex(const mec_gemm_args* a, void* stream);
 
 /* Tuning knobs (A/B benchmarking; defaults in brackets). Every handle owns its own copy of
  * the knobs and its own GEMM autotune cache, so two handles in one process never perturb

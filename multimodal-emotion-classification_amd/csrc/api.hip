@@ -295,8 +295,32 @@ int mec_conv_f16(const void* x, const void* w, const float* bias, const void* R,
     g.amode = A_CONV; g.A = x; g.B = reinterpret_cast<const f16*>(w); g.bias = bias; g.R = R;
     g.C16 = reinterpret_cast<f16*>(y); g.act = act;
     g.H = H; g.W = W; g.C = C; g.ks = ks; g.stride = stride; g.pad = pad;
-    g.OH = (H + 2 * pad - ks) / stride + 1; g.OW = (W + 2 * pad - ks) / stride + 1;
-    g.M = n * g.OH * g.OW; g.N = Cout; g.K = ks * ks * C;
+    MEC_TRY(set_conv_geometry(g, n));
+    g.N = Cout; g.K = ks * ks * C;
+    return launch_gemm(g, S(stream), nullptr, TAG_NONE);
+  })
+}
+
+int mec_gemm_ex(const mec_gemm_args* a, void* stream) {
+  API_GUARD({
+    MEC_REQUIRE(a, "mec_gemm_ex: null descriptor");
+    MEC_REQUIRE(a->amode == MEC_A_PLAIN || a->amode == MEC_A_CONV || a->amode == MEC_A_DUAL,
+                "mec_gemm_ex: amode must be MEC_A_PLAIN, MEC_A_CONV or MEC_A_DUAL");
+    MEC_REQUIRE((a->a_lo != 0) == (a->b_lo != 0), "mec_gemm_ex: a_lo and b_lo locate the lo planes together (both or neither)");
+    MEC_REQUIRE(a->oscale != 0.f && a->cscale != 0.f, "mec_gemm_ex: oscale and cscale must be set (1 = none)");
+    GemmParams g;
+    g.amode = a->amode; g.split = a->a_lo != 0;
+    g.A = a->A; g.a_lo = a->a_lo; g.A2 = a->A2; g.K1 = a->K1;
+    g.B = reinterpret_cast<const f16*>(a->B); g.b_lo = a->b_lo; g.oscale = a->oscale;
+    g.bias = a->bias; g.R = a->R; g.r_f32 = a->r_is_f32; g.r_lo = a->r_lo;
+    g.r_stats = reinterpret_cast<const float2*>(a->r_stats); g.r_g = a->r_gamma; g.r_b = a->r_beta;
+    g.C16 = reinterpret_cast<f16*>(a->C16); g.c_lo = a->C16 ? a->c_lo : 0; g.cscale = a->cscale; g.C32 = a->C32;
+    g.M = a->M; g.N = a->N; g.K = a->K; g.act = a->act;
+    if (a->amode != MEC_A_PLAIN) {  // conv / dual: M and K follow from the geometry
+      g.H = a->H; g.W = a->W; g.C = a->C; g.ks = a->ks; g.stride = a->stride; g.pad = a->pad;
+      MEC_TRY(set_conv_geometry(g, a->n));
+      g.K = a->amode == MEC_A_CONV ? a->ks * a->ks * a->C : a->K1 + a->C;
+    }
     return launch_gemm(g, S(stream), nullptr, TAG_NONE);
   })
 }
@@ -457,8 +481,8 @@ int mec_conv_f32(const float* x, const float* w, const float* bias, const float*
     GemmParams g;
     g.amode = A_CONV; g.A = x; g.B32 = w; g.bias = bias; g.R = R; g.r_f32 = 1; g.C32 = y; g.act = act;
     g.H = H; g.W = W; g.C = C; g.ks = ks; g.stride = stride; g.pad = pad;
-    g.OH = (H + 2 * pad - ks) / stride + 1; g.OW = (W + 2 * pad - ks) / stride + 1;
-    g.M = n * g.OH * g.OW; g.N = Cout; g.K = ks * ks * C;
+    MEC_TRY(set_conv_geometry(g, n));
+    g.N = Cout; g.K = ks * ks * C;
     return launch_gemm_f32(g, S(stream), nullptr, TAG_NONE);
   })
 }

@@ -19,6 +19,33 @@ constexpr int GBK = 64;
 // inside the encoder 128 x 128 is the fastest (text 8.22 ms vs 8.43 with 256 x 128 / 4 waves;
 // fused step 11.40 vs 11.48 ms).
 
+// Conv / dual geometry both engines require before any launch (a kernel walks OH x OW outputs per image and
+// steps the input by `stride`).
+int check_conv_geometry(const GemmParams& p) {
+  MEC_REQUIRE(p.ks >= 1, "conv geometry: ks >= 1");
+  MEC_REQUIRE(p.stride >= 1, "conv geometry: stride >= 1");
+  MEC_REQUIRE(p.pad >= 0, "conv geometry: pad >= 0");
+  MEC_REQUIRE(p.H >= 1 && p.W >= 1, "conv geometry: H >= 1 and W >= 1");
+  MEC_REQUIRE(p.OH >= 1 && p.OW >= 1, "conv geometry: OH >= 1 and OW >= 1 (ks within the padded input)");
+  return 0;
+}
+
+// The C-ABI entry points' geometry: n images of g's H x W x C input under g's ks / stride / pad. Validated
+// before the division by stride; sets OH, OW and M = n OH OW.
+int set_conv_geometry(GemmParams& g, int n) {
+  MEC_REQUIRE(n >= 1, "conv geometry: n >= 1");
+  MEC_REQUIRE(g.ks >= 1, "conv geometry: ks >= 1");
+  MEC_REQUIRE(g.stride >= 1, "conv geometry: stride >= 1");
+  MEC_REQUIRE(g.pad >= 0, "conv geometry: pad >= 0");
+  MEC_REQUIRE(g.H >= 1 && g.W >= 1, "conv geometry: H >= 1 and W >= 1");
+  MEC_REQUIRE(g.ks <= g.H + 2 * g.pad && g.ks <= g.W + 2 * g.pad,
+              "conv geometry: OH >= 1 and OW >= 1 (ks within the padded input)");
+  g.OH = (g.H + 2 * g.pad - g.ks) / g.stride + 1;
+  g.OW = (g.W + 2 * g.pad - g.ks) / g.stride + 1;
+  g.M = n * g.OH * g.OW;
+  return 0;
+}
+
 int launch_gemm(const GemmParams& p0, hipStream_t s, Prof* prof, int tag) {
   GemmParams p = p0;
   if (p.c_lo && !p.ovf) p.ovf = range_flag();  // split output: the calling handle's range flag
@@ -28,6 +55,9 @@ int launch_gemm(const GemmParams& p0, hipStream_t s, Prof* prof, int tag) {
   MEC_REQUIRE(p.A && p.B, "gemm: null operand");
   MEC_REQUIRE(p.C16 || p.C32, "gemm: no output");
   MEC_REQUIRE(!p.r_stats || (p.R && p.r_f32 && p.r_g && p.r_b), "gemm: deferred-LN residual needs f32 R, gamma, beta");
+  // the residual prefetch kernels read the lo plane only on split operands (gemm_glds.hip launch_cfg_act)
+  MEC_REQUIRE(!p.r_lo || (p.split && p.R && !p.r_f32), "gemm: r_lo needs split operands and an f16 residual");
+  if (p.amode == A_CONV || p.amode == A_DUAL) MEC_TRY(check_conv_geometry(p));
   if (p.amode == A_CONV) {
     MEC_REQUIRE(p.C % 64 == 0 && p.K == p.ks * p.ks * p.C, "conv: C % 64 != 0 or K != ks*ks*C");
   } else if (p.amode == A_DUAL) {
@@ -55,11 +85,12 @@ int launch_gemm(const GemmParams& p0, hipStream_t s, Prof* prof, int tag) {
                                 : !opt().gemm_x3_order ? (tag == TAG_BERT_FFN1 ? 10256 : 0)
                                 : pin);
   } else if (opt().conv3x3_direct && !opt().gemm_bn && p.amode == A_CONV && p.ks == 3 && p.stride == 1 && p.pad == 1 && p.H == 56 &&
-      p.W == 56 && p.C == 64 && p.N == 64 && p.act == ACT_RELU && !p.R && p.C16 && !p.C32 && p.M % (56 * 56) == 0)
+      p.W == 56 && p.C == 64 && p.N == 64 && p.act == ACT_RELU && !p.R && p.bias && p.C16 && !p.C32 && !p.c_lo &&
+      p.oscale == 1.f && p.M % (56 * 56) == 0)
     rc = launch_conv3x3_c64(reinterpret_cast<const f16*>(p.A), p.B, p.bias, p.C16, p.M / (56 * 56), 56, 64, 64, s);
   else if (opt().conv3x3_halo && !opt().gemm_bn && p.amode == A_CONV && p.ks == 3 && p.stride == 1 && p.pad == 1 &&
            p.H == p.W && p.OH == p.H && p.OW == p.W && conv3x3_halo_supported(p.H, p.C, p.N) && p.act == ACT_RELU &&
-           !p.R && p.bias && p.C16 && !p.C32 && p.M % (p.H * p.W) == 0)
+           !p.R && p.bias && p.C16 && !p.C32 && !p.c_lo && p.oscale == 1.f && p.M % (p.H * p.W) == 0)
     rc = launch_conv3x3_halo(reinterpret_cast<const f16*>(p.A), p.B, p.bias, p.C16, p.M / (p.H * p.W), p.H, p.C, s);
   else
     rc = launch_gemm_glds(p, s, opt().gemm_bn ? opt().gemm_bn : (tag > 0 && tag < TAG_COUNT ? opt().gemm_bn_tag[tag] : 0));

@@ -319,6 +319,7 @@ int launch_gemm_f32(const GemmParams& p, hipStream_t s, Prof* prof, int tag) {
   MEC_REQUIRE(!p.R || p.r_f32, "gemm_f32: residual must be f32");
   MEC_REQUIRE(!p.r_stats, "gemm_f32: no deferred LayerNorm on the fp32 path");
   if (p.amode == A_CONV) {
+    MEC_TRY(check_conv_geometry(p));
     MEC_REQUIRE(p.C % 32 == 0 && p.K == p.ks * p.ks * p.C, "conv_f32: C % 32 != 0 or K != ks*ks*C");
   } else {
     MEC_REQUIRE(p.amode == A_PLAIN, "gemm_f32: plain or conv A only");

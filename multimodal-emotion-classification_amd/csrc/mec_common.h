@@ -350,6 +350,11 @@ struct GemmParams {
   int x3_prio = 0;   // opt().gemm_x3_prio (the same kernels)
 };
 
+// conv / dual geometry (gemm.hip): what both engines require of ks, stride, pad and the extents before a
+// launch; and the C-ABI entries' form, which validates n and the rest before dividing by stride and sets
+// OH, OW and M = n OH OW
+int check_conv_geometry(const GemmParams& p);
+int set_conv_geometry(GemmParams& g, int n);
 int launch_gemm(const GemmParams& p, hipStream_t s, Prof* prof, int tag);
 int launch_gemm_glds(const GemmParams& p, hipStream_t s, int force_bn);
 // 3x3/1 conv 64 -> 64 on 56x56 (+ BN shift + ReLU) as a halo-tile kernel (conv3x3.hip);

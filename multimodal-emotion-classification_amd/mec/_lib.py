@@ -18,6 +18,25 @@ c_int = ctypes.c_int
 c_fp = ctypes.POINTER(ctypes.c_float)
 c_dp = ctypes.POINTER(ctypes.c_double)
 
+
+class GemmArgs(ctypes.Structure):
+    """include/mec.h mec_gemm_args (mec_gemm_ex's descriptor), field for field. amode: A_PLAIN /
+    A_CONV / A_DUAL below; oscale and cscale default to 1 (none)."""
+    _fields_ = [('amode', c_int), ('A', c_vp), ('a_lo', ctypes.c_longlong), ('A2', c_vp), ('K1', c_int),
+                ('B', c_vp), ('b_lo', ctypes.c_longlong), ('oscale', ctypes.c_float), ('bias', c_vp),
+                ('R', c_vp), ('r_is_f32', c_int), ('r_lo', ctypes.c_longlong),
+                ('r_stats', c_vp), ('r_gamma', c_vp), ('r_beta', c_vp),
+                ('C16', c_vp), ('c_lo', ctypes.c_longlong), ('cscale', ctypes.c_float), ('C32', c_vp),
+                ('M', c_int), ('N', c_int), ('K', c_int), ('act', c_int),
+                ('n', c_int), ('H', c_int), ('W', c_int), ('C', c_int), ('ks', c_int), ('stride', c_int),
+                ('pad', c_int)]
+
+    def __init__(self, **kw):
+        super().__init__(**{'oscale': 1.0, 'cscale': 1.0, **kw})
+
+
+A_PLAIN, A_CONV, A_DUAL = 0, 1, 2
+
 # name -> (restype, argtypes); mirrors include/mec.h one to one.
 SIGNATURES = {
     'mec_version': (ctypes.c_char_p, []),
@@ -46,6 +65,7 @@ SIGNATURES = {
     'mec_gemm_f32': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp]),
     'mec_conv_f32': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                              c_int, c_int, c_vp]),
+    'mec_gemm_ex': (c_int, [ctypes.POINTER(GemmArgs), c_vp]),
     'mec_set_option': (c_int, [ctypes.c_char_p, c_int]),
     'mec_model_set_option': (c_int, [c_vp, ctypes.c_char_p, c_int]),
     'mec_build_flags': (c_int, []),

@@ -94,6 +94,98 @@ def test_c_abi_argument_errors_without_gpu():
     assert b'null model' in lib.mec_last_error()
 
 
+BAD_GEOMETRY = {  # (n, H, W, ks, stride, pad) -> the requirement the message names
+    'stride 0': ((2, 8, 8, 3, 0, 1), b'stride >= 1'),
+    'ks 0': ((2, 8, 8, 0, 1, 0), b'ks >= 1'),
+    'negative pad': ((2, 8, 8, 3, 1, -1), b'pad >= 0'),
+    'ks larger than the padded input': ((2, 1, 1, 5, 1, 0), b'OH >= 1 and OW >= 1'),
+    'ks larger than the padded width only': ((2, 8, 2, 5, 1, 1), b'OH >= 1 and OW >= 1'),
+    'ks past the input at a stride that rounds to one output': ((2, 1, 1, 2, 2, 0), b'OH >= 1 and OW >= 1'),
+    'n 0': ((0, 8, 8, 3, 1, 1), b'n >= 1'),
+}
+
+
+@pytest.mark.parametrize('entry', ['mec_conv_f16', 'mec_conv_f32', 'mec_gemm_ex conv', 'mec_gemm_ex split conv',
+                                   'mec_gemm_ex dual'])
+@pytest.mark.parametrize('case', list(BAD_GEOMETRY))
+def test_conv_geometry_rejected_before_any_launch(entry, case):
+    """Every conv / dual entry point returns -1 on a geometry with no outputs (or a zero stride, which
+    was a host division by zero) and names the requirement; the check precedes every device call, so
+    the fake non-null pointers are never read and this runs without a GPU."""
+    import ctypes
+    lib = _lib.load()
+    (n, H, W, ks, stride, pad), msg = BAD_GEOMETRY[case]
+    C = Cout = 64
+    p = ctypes.c_void_p(0x1000)
+    if entry.startswith('mec_conv'):
+        rc = getattr(lib, entry)(p, p, None, None, p, n, H, W, C, Cout, ks, stride, pad, 0, None)
+    else:
+        dual = entry.endswith('dual')
+        a = _lib.GemmArgs(amode=_lib.A_DUAL if dual else _lib.A_CONV, A=p, B=p, C32=p, N=Cout, n=n, H=H, W=W, C=C,
+                          ks=ks, stride=stride, pad=pad, M=77, K=64)
+        if dual:
+            a.A2, a.K1 = p, 64
+        if 'split' in entry:
+            a.a_lo = a.b_lo = 1 << 20
+        rc = lib.mec_gemm_ex(ctypes.byref(a), None)
+    assert rc == -1
+    assert msg in lib.mec_last_error(), lib.mec_last_error()
+
+
+def test_gemm_ex_descriptor_errors_without_gpu():
+    """mec_gemm_ex's own argument checks, and the engine's for the modes only it reaches."""
+    import ctypes
+    lib = _lib.load()
+    p = ctypes.c_void_p(0x1000)
+    assert lib.mec_gemm_ex(None, None) == -1 and b'null descriptor' in lib.mec_last_error()
+    ok = dict(A=p, B=p, C32=p, M=64, N=64, K=64)
+    for kw, msg in ((dict(amode=3), b'amode'), (dict(a_lo=4096), b'a_lo and b_lo'), (dict(oscale=0.0), b'oscale'),
+                    (dict(cscale=0.0), b'cscale'), (dict(N=96), b'N % 64'), (dict(K=32), b'K % 64'),
+                    (dict(C32=None), b'no output'), (dict(M=0), b'empty shape'),
+                    (dict(R=p, r_lo=4096), b'r_lo needs split operands'),
+                    (dict(R=p, r_lo=4096, a_lo=4096, b_lo=4096, r_is_f32=1), b'r_lo needs split operands'),
+                    (dict(R=p, r_is_f32=1, r_stats=p), b'deferred-LN residual'),
+                    (dict(amode=_lib.A_DUAL, n=1, H=8, W=8, C=64, ks=1, stride=1, pad=0, K1=64), b'dual gemm'),
+                    (dict(amode=_lib.A_DUAL, A2=p, n=1, H=8, W=8, C=64, ks=3, stride=1, pad=1, K1=64), b'dual gemm'),
+                    (dict(amode=_lib.A_CONV, n=1, H=8, W=8, C=32, ks=2, stride=1, pad=0), b'C % 64')):
+        a = _lib.GemmArgs(**{**ok, **kw})
+        assert lib.mec_gemm_ex(ctypes.byref(a), None) == -1, kw
+        assert msg in lib.mec_last_error(), (kw, lib.mec_last_error())
+
+
+@pytest.mark.parametrize('geom', ['G1', 'G2', 'G3', 'G4', 'G5'])
+def test_gemm_mode_references_vs_torch_conv2d_f64(geom):
+    """The float64 NHWC conv, tap-view and dual-gather helpers the GPU GEMM-mode tests compare kernels
+    with (tests/gemm_ref.py), against torch.nn.functional.conv2d in float64."""
+    import torch
+    import gemm_ref
+    n, H, W, C, Cout, ks, stride, pad = gemm_ref.GEOMETRIES[geom]
+    rng = np.random.default_rng(H * W + C)
+    x = rng.standard_normal((n, H, W, C))
+    w = rng.standard_normal((Cout, ks, ks, C))
+    xt = torch.from_numpy(x).permute(0, 3, 1, 2)
+
+    def conv(wt, s, p):
+        return torch.nn.functional.conv2d(xt, torch.from_numpy(wt).permute(0, 3, 1, 2), stride=s,
+                                          padding=p).permute(0, 2, 3, 1).numpy()
+
+    ref = conv(w, stride, pad)
+    got = gemm_ref.conv_nhwc_f64(x, w, stride, pad)
+    assert got.shape == ref.shape == (n, gemm_ref.out_extent(H, ks, stride, pad),
+                                      gemm_ref.out_extent(W, ks, stride, pad), Cout)
+    assert np.abs(got - ref).max() <= 1e-12 * np.abs(ref).max()
+    # one-hot tap weights select the tap view exactly (products by 1.0 and sums with 0.0)
+    for kh in range(ks):
+        for kw in range(ks):
+            sel = np.zeros((C, ks, ks, C))
+            sel[np.arange(C), kh, kw, np.arange(C)] = 1.0
+            assert np.array_equal(conv(sel, stride, pad), gemm_ref.tap_view(x, kh, kw, ks, stride, pad)), (kh, kw)
+    # the dual second source: a 1x1 identity conv at stride 1 and 2, unpadded
+    for s in (1, 2):
+        g = gemm_ref.dual_gather(x, s)
+        assert np.array_equal(g, conv(np.eye(C).reshape(C, 1, 1, C), s, 0).reshape(-1, C))
+
+
 def test_create_opt_parses_its_option_list_without_gpu():
     """mec_create_opt validates its "key=value,..." list (the mec_set_option keys and values) before
     any device call; mec_model_x3_report needs a handle."""
