@@ -369,10 +369,6 @@ int set_option(Options& o, const std::string& k, int value) {
   if (k == "mbv2_x3_sesw" && (value == 0 || value == 1)) { o.mbv2_x3_sesw = value; return 0; }
   if (k == "x3_plane_scale" && (value == 0 || value == 1)) { o.x3_plane_scale = value; return 0; }
   if (k == "x3_headroom" && value >= 0 && value <= 24) { o.x3_headroom = value; return 0; }
-  if (k == "gemm_x3_restage" && value >= 0 && value <= 2) { o.gemm_x3_restage = value; return 0; }
-  if (k == "gemm_x3_stagger" && value >= 0 && value <= 200) { o.gemm_x3_stagger = value; return 0; }
-  if (k == "gemm_x3_late_dma" && value >= 0 && value <= 3) { o.gemm_x3_late_dma = value; return 0; }
-  if (k == "gemm_x3_prio" && (value == 0 || value == 1)) { o.gemm_x3_prio = value; return 0; }
   if (k == "qkv_x3_late_dma" && value >= 0 && value <= 2) { o.qkv_x3_late_dma = value; return 0; }
   if (k == "mbv2_layered" && (value == 0 || (value >= 7 && value <= 17))) { o.mbv2_layered = value; return 0; }
   if (k == "mbv2_layered16" && (value == 0 || (value >= 7 && value <= 17))) { o.mbv2_layered16 = value; return 0; }

@@ -813,14 +813,17 @@ int AudioModel::forward(const float* wave, int B, int L, float* feat, float* tun
   MEC_REQUIRE(L >= A_NFFT / 2 + 1 && L / A_HOP + 1 <= A_TMAX, "audio: n_samples out of range (1025 .. 2^21)");
   const int T = 1 + L / A_HOP;  // center=True frames
   const size_t fr = (size_t)B * T;
-  const size_t need = fr * (A_NBIN * 4 + A_NMEL * 4 + 4 * 8 + A_CMAX * 8 + 4) + 1024;
-  if (ws.bytes < need) MEC_TRY(ws.ensure(need));
-  char* p = ws.as<char>();
-  double* scal = reinterpret_cast<double*>(p); p += fr * 4 * 8;
-  float2* cand = reinterpret_cast<float2*>(p); p += fr * A_CMAX * 8;
-  float* pw = reinterpret_cast<float*>(p); p += fr * A_NBIN * 4;
-  float* mdb = reinterpret_cast<float*>(p); p += fr * A_NMEL * 4;
-  int* cc = reinterpret_cast<int*>(p);
+  double* scal;
+  float2* cand;
+  float *pw, *mdb;
+  int* cc;
+  MEC_TRY(carve(ws, [&](Carver& c) {
+    scal = c.take<double>(fr * 4);
+    cand = c.take<float2>(fr * A_CMAX);
+    pw = c.take<float>(fr * A_NBIN);
+    mdb = c.take<float>(fr * A_NMEL);
+    cc = c.take<int>(fr);
+  }));
   const char* tb0 = tables.as<char>();
   AudioTables tb;
   tb.hann = reinterpret_cast<const double*>(tb0 + off_hann);

@@ -1159,32 +1159,26 @@ int TextModel::forward(const int32_t* ids, const int32_t* mask, int B, int L, fl
   // workspace: h32 | t32 (f32 [M,768]) ; h16 | ctx16 (f16 [M,768]) ; qkv16 [M,2304] / i16 [M,3072]
   // + the [CLS]-row buffers of the last layer (bert_cls_last): h32c | t32c (f32 [B,768]) ; h16c | qc |
   // ctxc (f16 [B,768]) ; fc (f16 [B,3072]) ; st1c | st2c ([B] float2)
-  const size_t need = (size_t)M * BH * 4 * 2 + (size_t)M * BH * 2 * 2 + (size_t)M * BI * 2 + (size_t)B * BH * 4 +
-                      (size_t)M * 8 * 2 + (size_t)B * BH * 4 * 2 + (size_t)B * BH * 2 * 3 + (size_t)B * BI * 2 +
-                      (size_t)B * 8 * 2;
-  if (M > ws_tokens) {
-    MEC_TRY(ws.ensure(need));
-    ws_tokens = M;
-  }
-  char* p = ws.as<char>();
-  float* h32 = reinterpret_cast<float*>(p); p += (size_t)M * BH * 4;
-  float* t32 = reinterpret_cast<float*>(p); p += (size_t)M * BH * 4;
-  f16* h16 = reinterpret_cast<f16*>(p); p += (size_t)M * BH * 2;
-  f16* ctx16 = reinterpret_cast<f16*>(p); p += (size_t)M * BH * 2;
-  f16* big16 = reinterpret_cast<f16*>(p);  // qkv16 [M,2304] then i16 [M,3072]
-  p += (size_t)M * BI * 2;
-  float* pooled = reinterpret_cast<float*>(p);  // [B,768]
-  p += (size_t)B * BH * 4;
-  float2* st1 = reinterpret_cast<float2*>(p);  // LN1 row stats [M]
-  float2* st2 = st1 + M;                       // LN2 row stats [M]
-  p += (size_t)M * 8 * 2;
-  float* h32c = reinterpret_cast<float*>(p); p += (size_t)B * BH * 4;
-  float* t32c = reinterpret_cast<float*>(p); p += (size_t)B * BH * 4;
-  f16* h16c = reinterpret_cast<f16*>(p); p += (size_t)B * BH * 2;
-  f16* qc = reinterpret_cast<f16*>(p); p += (size_t)B * BH * 2;
-  f16* ctxc = reinterpret_cast<f16*>(p); p += (size_t)B * BH * 2;
-  f16* fc = reinterpret_cast<f16*>(p); p += (size_t)B * BI * 2;
-  float2* st1c = reinterpret_cast<float2*>(p);
+  float *h32, *t32, *pooled, *h32c, *t32c;
+  f16 *h16, *ctx16, *big16, *h16c, *qc, *ctxc, *fc;
+  float2 *st1, *st1c;
+  MEC_TRY(carve(ws, [&](Carver& c) {
+    h32 = c.take<float>((size_t)M * BH);
+    t32 = c.take<float>((size_t)M * BH);
+    h16 = c.take<f16>((size_t)M * BH);
+    ctx16 = c.take<f16>((size_t)M * BH);
+    big16 = c.take<f16>((size_t)M * BI);  // qkv16 [M,2304] then i16 [M,3072]
+    pooled = c.take<float>((size_t)B * BH);
+    st1 = c.take<float2>((size_t)M * 2);  // LN1 | LN2 row stats [M] each
+    h32c = c.take<float>((size_t)B * BH);
+    t32c = c.take<float>((size_t)B * BH);
+    h16c = c.take<f16>((size_t)B * BH);
+    qc = c.take<f16>((size_t)B * BH);
+    ctxc = c.take<f16>((size_t)B * BH);
+    fc = c.take<f16>((size_t)B * BI);
+    st1c = c.take<float2>((size_t)B * 2);
+  }));
+  float2* st2 = st1 + M;
   float2* st2c = st1c + B;
   const bool cls_last = opt().bert_cls_last != 0;
 

@@ -159,19 +159,19 @@ int TextModel::forward_f32(const int32_t* ids, const int32_t* mask, int B, int L
   const int M = B * L;
   // workspace: h32 | t32 | ctx32 (f32 [M,768]) ; big32 f32 [M,3072] (qkv [M,2304], then FFN) ; pooled [B,768] ;
   // the [CLS]-row buffers of the last layer (bert_cls_last): h32c | t32c | qc | ctxc [B,768], fc [B,3072]
-  const size_t need = (size_t)M * H * 4 * 3 + (size_t)M * FF * 4 + (size_t)B * H * 4 * 5 + (size_t)B * FF * 4;
-  if (ws.bytes < need) MEC_TRY(ws.ensure(need));
-  char* p = ws.as<char>();
-  float* h32 = reinterpret_cast<float*>(p); p += (size_t)M * H * 4;
-  float* t32 = reinterpret_cast<float*>(p); p += (size_t)M * H * 4;
-  float* ctx32 = reinterpret_cast<float*>(p); p += (size_t)M * H * 4;
-  float* big32 = reinterpret_cast<float*>(p); p += (size_t)M * FF * 4;
-  float* pooled = reinterpret_cast<float*>(p); p += (size_t)B * H * 4;
-  float* h32c = reinterpret_cast<float*>(p); p += (size_t)B * H * 4;
-  float* t32c = reinterpret_cast<float*>(p); p += (size_t)B * H * 4;
-  float* qc = reinterpret_cast<float*>(p); p += (size_t)B * H * 4;
-  float* ctxc = reinterpret_cast<float*>(p); p += (size_t)B * H * 4;
-  float* fc = reinterpret_cast<float*>(p);
+  float *h32, *t32, *ctx32, *big32, *pooled, *h32c, *t32c, *qc, *ctxc, *fc;
+  MEC_TRY(carve(ws, [&](Carver& c) {
+    h32 = c.take<float>((size_t)M * H);
+    t32 = c.take<float>((size_t)M * H);
+    ctx32 = c.take<float>((size_t)M * H);
+    big32 = c.take<float>((size_t)M * FF);
+    pooled = c.take<float>((size_t)B * H);
+    h32c = c.take<float>((size_t)B * H);
+    t32c = c.take<float>((size_t)B * H);
+    qc = c.take<float>((size_t)B * H);
+    ctxc = c.take<float>((size_t)B * H);
+    fc = c.take<float>((size_t)B * FF);
+  }));
   const bool cls_last = opt().bert_cls_last != 0;
 
   MEC_TRY(launch_bert_embed_ln(ids, M, L, emb.as<float>(), h32, nullptr, s));
@@ -266,26 +266,26 @@ int TextModel::forward_x3(const int32_t* ids, const int32_t* mask, int B, int L,
   // (f16 planes 2x[B,768]) ; fsc (f16 planes 2x[B,3072])
   const long long BHc = (long long)B * H, BFc = (long long)B * FF;
   // + the LayerNorm row stats st1 | st2 ([M] float2; deferred LayerNorm, below) and st2c ([B] float2)
-  const size_t need = (size_t)MH * 4 * 2 + (size_t)MH * 2 * 4 + (size_t)MF * 4 + (size_t)B * H * 4 +
-                      (size_t)BHc * 4 * 2 + (size_t)BHc * 4 * 3 + (size_t)BFc * 4 + (size_t)M * 8 * 2 + (size_t)B * 8;
-  if (ws.bytes < need) MEC_TRY(ws.ensure(need));
-  char* p = ws.as<char>();
-  float* h32 = reinterpret_cast<float*>(p); p += (size_t)MH * 4;
-  float* t32 = reinterpret_cast<float*>(p); p += (size_t)MH * 4;
-  f16* hs = reinterpret_cast<f16*>(p); p += (size_t)MH * 2 * 2;
-  f16* cs = reinterpret_cast<f16*>(p); p += (size_t)MH * 2 * 2;
-  float* big32 = reinterpret_cast<float*>(p);
-  f16* bigs = reinterpret_cast<f16*>(p); p += (size_t)MF * 4;
-  float* pooled = reinterpret_cast<float*>(p); p += (size_t)B * H * 4;
-  float* h32c = reinterpret_cast<float*>(p); p += (size_t)BHc * 4;
-  float* t32c = reinterpret_cast<float*>(p); p += (size_t)BHc * 4;
-  f16* hsc = reinterpret_cast<f16*>(p); p += (size_t)BHc * 4;
-  f16* qsc = reinterpret_cast<f16*>(p); p += (size_t)BHc * 4;
-  f16* csc = reinterpret_cast<f16*>(p); p += (size_t)BHc * 4;
-  f16* fsc = reinterpret_cast<f16*>(p); p += (size_t)BFc * 4;
-  float2* st1 = reinterpret_cast<float2*>(p);  // LN1 row stats [M]
-  float2* st2 = st1 + M;                       // LN2 row stats [M]
-  float2* st2c = st2 + M;                      // LN2 row stats of the [CLS] rows [B]
+  float *h32, *t32, *pooled, *h32c, *t32c;
+  f16 *hs, *cs, *bigs, *hsc, *qsc, *csc, *fsc;
+  float2 *st1, *st2c;
+  MEC_TRY(carve(ws, [&](Carver& c) {
+    h32 = c.take<float>((size_t)MH);
+    t32 = c.take<float>((size_t)MH);
+    hs = c.take<f16>((size_t)MH * 2);
+    cs = c.take<f16>((size_t)MH * 2);
+    bigs = c.take<f16>((size_t)MF * 2);
+    pooled = c.take<float>((size_t)B * H);
+    h32c = c.take<float>((size_t)BHc);
+    t32c = c.take<float>((size_t)BHc);
+    hsc = c.take<f16>((size_t)BHc * 2);
+    qsc = c.take<f16>((size_t)BHc * 2);
+    csc = c.take<f16>((size_t)BHc * 2);
+    fsc = c.take<f16>((size_t)BFc * 2);
+    st1 = c.take<float2>((size_t)M * 2);  // LN1 | LN2 row stats [M] each
+    st2c = c.take<float2>((size_t)B);     // LN2 row stats of the [CLS] rows
+  }));
+  float2* st2 = st1 + M;
   const bool cls_last = opt().bert_cls_last != 0;
   const int gelu_act = opt().gelu_x3 ? ACT_GELU_F32 : ACT_GELU_EXACT;  // FFN1's erf GELU
 

@@ -220,12 +220,8 @@ int launch_conv3x3_c64(const f16* x, const f16* w, const float* bias, f16* y, in
                        hipStream_t s) {
   MEC_REQUIRE(H == C3_H && C == C3_C && Cout == C3_C, "conv3x3_c64: needs 56x56, 64 -> 64 channels");
   MEC_REQUIRE(x && w && bias && y && B > 0, "conv3x3_c64: bad arguments");
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    MEC_HIP(hipGetDevice(&dev));
-    MEC_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-  }
+  const int ncu = cu_count();
+  if (ncu < 0) return -1;
   const int ntiles = B * (C3_H / C3_TR);
   const dim3 grd(std::min(ntiles, ncu)), blk(256);
   switch (opt().conv3x3_debug) {  // probe builds (wrong results): 1 no next-tile DMA, 2 no stores, 4 no LDS reads

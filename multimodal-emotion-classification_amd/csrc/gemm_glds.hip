@@ -30,7 +30,7 @@ namespace mec {
 __device__ __attribute__((aligned(64))) uint4 g_zero_page[16];
 
 template <int BM, int BN, int WM, int WN, int NS, int AM, int DBG = 0, int MF = 32, int BK = 64, int PRE = 0,
-          int ACT = -1, int SP = 0, int ER = 0>
+          int ACT = -1, int SP = 0>
 __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4) ? 2 : 1) void gemm_glds_kernel(const GemmParams p) {
   // MF: 32 = v_mfma_f32_32x32x16_f16 tiles, 16 = v_mfma_f32_16x16x32_f16 tiles
   // DBG (probe builds only): 1 = no operand loads inside the K loop, 2 = no epilogue
@@ -47,14 +47,11 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4) ? 2 : 1) void gemm_gld
   static_assert(BK == 64 || BK == 32, "BK");
   static_assert(SP == 0 || PRE == 0 || PRE == 3, "split operands: split residual prefetch only");
   static_assert(SP != 2 || MF == 16, "interleaved split: 16x16x32 tiles only");
-  // ER (early restage, opt().gemm_x3_restage; interleaved split tiles with a 2-stage ring and 32-deep stages):
-  // each k step reads its whole stage into fragment registers first, so once every wave holds them the
-  // stage is refilled with k step t + 2 while step t's MFMAs run -- two steps in flight on two buffers
-  // instead of one (bert_qkv_attn_x3_kernel's schedule). Same fragments, same MFMA order: same bits.
-  // NS = 1 (tile 72128): one stage, read whole into fragments and restaged for step t + 1 under step t's MFMAs;
-  // 48 KB of LDS lets two workgroups share a CU, so one's barriers, loads and epilogue run under the other's
-  // MFMAs
-  constexpr bool ERS = ER != 0 && SP == 2 && (NS == 2 || NS == 1) && BK == 32 && DBG == 0;
+  // NS = 1 (tile 72128, interleaved split operands): one stage, read whole into fragment registers; once every
+  // wave holds them the stage is refilled for step t + 1 under step t's MFMAs (bert_qkv_attn_x3_kernel's
+  // schedule). 48 KB of LDS lets two workgroups share a CU, so one's barriers, loads and epilogue run under
+  // the other's MFMAs. Same fragments, same MFMA order as the ring tiles: same bits.
+  static_assert(NS != 1 || (SP == 2 && BK == 32 && DBG == 0), "one-stage tile: interleaved split operands only");
   constexpr int CH = BK / 8;                   // 16-B chunks per LDS row
   constexpr int RPI = 64 / CH;                 // rows per glds wave-instruction (1 KB)
   constexpr int NW = WM * WN;
@@ -90,10 +87,6 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4) ? 2 : 1) void gemm_gld
   int bm, bn;
   tile_coords(bid, nbm, nbn, p.group_m, bm, bn);
   const int m0 = bm * BM, n0 = bn * BN;
-  if (p.stagger && (int)blockIdx.x >= p.stagger_lo && (int)blockIdx.x < p.stagger_hi) {
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    while (__builtin_amdgcn_s_memrealtime() - t0 < (unsigned long long)p.stagger) __builtin_amdgcn_s_sleep(16);
-  }
 
   // ---- per-lane DMA sources: lane -> (row in its 8-row group, physical chunk)
   const int lrow = lane / CH, pchunk = lane % CH;
@@ -221,18 +214,17 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4) ? 2 : 1) void gemm_gld
 
   const int nk = SP == 1 ? 3 * nk0 : nk0;
 #pragma unroll
-  for (int s = 0; s < (ERS ? NS : NS - 1); ++s)
+  for (int s = 0; s < (NS == 1 ? 1 : NS - 1); ++s)
     if (s < nk) issue(s, s);
 
   const int lr = lane & 31, lh = lane >> 5;
-  if constexpr (ERS) {
+  if constexpr (NS == 1) {
     const int l16 = lane & 15, lq = lane >> 4;
     for (int t = 0; t < nk; ++t) {
-      if (NS == 2 && t + 1 < nk) wait_vm<LPT>();  // step t landed; step t + 1 may stay in flight
-      else wait_vm<0>();
+      wait_vm<0>();
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      const f16* sA = smem + (NS == 1 ? 0 : (t & 1)) * STAGE;
+      const f16* sA = smem;
       const f16* sB = sA + BM * BK;
       half8 af[2][TI], bf[2][TJ];  // [plane: 0 hi, 1 lo]
 #pragma unroll
@@ -251,7 +243,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4) ? 2 : 1) void gemm_gld
       __builtin_amdgcn_sched_barrier(0);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();  // every wave holds its fragments: the stage is free
-      if (t + NS < nk) issue(NS == 1 ? 0 : (t & 1), t + NS);
+      if (t + 1 < nk) issue(0, t + 1);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int i = 0; i < TI; ++i)
@@ -291,32 +283,24 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4) ? 2 : 1) void gemm_gld
     (void)ahead;
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    // late_dma (split tiles, opt().gemm_x3_late_dma): the upper half of the waves -- the second wave of each
-    // SIMD -- issues its share of the next stage's DMA after its first term group of MFMAs instead of right
-    // after the barrier, so the two waves of a SIMD never both sit in the DMA issue (≈ 60-185 cycles per
-    // instruction, MI355X_MICROARCH.md) while the matrix core idles. The stage is free either way (every
-    // wave passed this barrier, so step t - 1's reads of it are done); same fragments and MFMAs: same bits
-    // (late_dma 1: after the lo.hi terms; 2: after the hi.lo terms; 3: the hi planes after lo.hi, the lo planes
-    // after hi.lo)
-    // (measured and dropped, DESIGN.md §0: the first half of the waves issuing after its first fragment reads;
-    // the second half issuing after the first I1 rows of lo.hi, or halfway through hi.lo)
-    const bool late = SP == 2 && p.late_dma && wave >= NW / 2;
+    // Late DMA issue (interleaved split tiles): the upper half of the waves -- the second wave of each
+    // SIMD -- issues its share of the next stage's DMA after the lo.hi term group of the step's first k chunk
+    // instead of right after the barrier, so the two waves of a SIMD never both sit in the DMA issue
+    // (≈ 60-185 cycles per instruction, MI355X_MICROARCH.md) while the matrix core idles. The stage is free
+    // either way (every wave passed this barrier, so step t - 1's reads of it are done); same fragments and
+    // MFMAs: same bits
+    // (measured and dropped, DESIGN_HISTORY.md: the first half of the waves issuing after its first fragment
+    // reads; the second half issuing after the first I1 rows of lo.hi, halfway through hi.lo, after hi.lo, or
+    // its hi planes after lo.hi and lo planes after hi.lo; every wave issuing right after the barrier; MFMA
+    // sections at wave priority 1; an early restage of the 2-stage rings; a start stagger between the
+    // workgroups sharing a CU)
+    const bool late = SP == 2 && wave >= NW / 2;
     const bool nxt = DBG != 1 && t + NS - 1 < nk;
     if (nxt && !late) issue((t + NS - 1) % NS, t + NS - 1);
-    // x3_prio (opt().gemm_x3_prio): a wave's MFMA sections at wave priority 1, its DMA issue and the barrier at 0,
-    // so the SIMD's other wave, issuing DMA, takes the issue slots the MFMAs leave
-    const bool prio = SP == 2 && p.x3_prio;
-    if (prio) __builtin_amdgcn_s_setprio(1);
-    auto issue_late = [&](int part) {  // part: 0 = both planes, 1 = hi planes, 2 = lo planes
-      if constexpr (SP == 2) {
-        const int st = (t + NS - 1) % NS, kt = t + NS - 1;
-        __builtin_amdgcn_sched_barrier(0);
-        if (prio) __builtin_amdgcn_s_setprio(0);
-        if (part != 2) issue_plane(st, kt, 0, 0, 0);
-        if (part != 1) issue_plane(st, kt, 1, p.a_lo, p.b_lo);
-        if (prio) __builtin_amdgcn_s_setprio(1);
-        __builtin_amdgcn_sched_barrier(0);
-      }
+    auto issue_late = [&]() {
+      __builtin_amdgcn_sched_barrier(0);
+      issue((t + NS - 1) % NS, t + NS - 1);
+      __builtin_amdgcn_sched_barrier(0);
     };
     const f16* sA = smem + ((DBG == 1 ? 0 : t) % NS) * STAGE;
     const f16* sB = sA + BM * BK;
@@ -396,17 +380,12 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4) ? 2 : 1) void gemm_gld
 #pragma unroll
           for (int j = 0; j < TJ; ++j)
             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[1][i], bf[0][j], acc[i][j], 0, 0, 0);
-        if (late && s == 0 && nxt && (p.late_dma == 1 || p.late_dma == 3)) issue_late(p.late_dma == 1 ? 0 : 1);
+        if (late && s == 0 && nxt) issue_late();
 #pragma unroll
         for (int i = 0; i < TI; ++i)
 #pragma unroll
           for (int j = 0; j < TJ; ++j)
             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[0][i], bf[1][j], acc[i][j], 0, 0, 0);
-        if (late && s == 0 && nxt && (p.late_dma == 2 || p.late_dma == 3)) issue_late(p.late_dma == 2 ? 0 : 2);
-        if (prio && s == KS - 1) {
-          __builtin_amdgcn_sched_barrier(0);
-          __builtin_amdgcn_s_setprio(0);
-        }
 #pragma unroll
         for (int i = 0; i < TI; ++i)
 #pragma unroll
@@ -867,18 +846,18 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmParams p) {
 
 // BM=256 tiles: (BN, WM, WN, NS)
 
-// K-interleaved split operands (16x16x32, 32-deep stages) in each A mode; ER = the early-restage schedule
-template <int BM, int BN, int WM, int WN, int NS, int BK, int ER>
+// K-interleaved split operands (16x16x32, 32-deep stages) in each A mode
+template <int BM, int BN, int WM, int WN, int NS, int BK>
 static int launch_x3i(const GemmParams& p, hipStream_t s, int nwg, dim3 blk) {
   if (BM * BN <= 128 * 128 && opt().gemm_prefetch_r && p.amode == A_PLAIN && p.R && p.r_lo && p.K <= 512) {
     if constexpr (BM * BN <= 128 * 128)
-      hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, WM, WN, NS, A_PLAIN, 0, 16, BK, 3, -1, 2, ER>), dim3(nwg), blk, 0, s, p);
+      hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, WM, WN, NS, A_PLAIN, 0, 16, BK, 3, -1, 2>), dim3(nwg), blk, 0, s, p);
   } else if (p.amode == A_PLAIN)
-    hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, WM, WN, NS, A_PLAIN, 0, 16, BK, 0, -1, 2, ER>), dim3(nwg), blk, 0, s, p);
+    hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, WM, WN, NS, A_PLAIN, 0, 16, BK, 0, -1, 2>), dim3(nwg), blk, 0, s, p);
   else if (p.amode == A_CONV)
-    hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, WM, WN, NS, A_CONV, 0, 16, BK, 0, -1, 2, ER>), dim3(nwg), blk, 0, s, p);
+    hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, WM, WN, NS, A_CONV, 0, 16, BK, 0, -1, 2>), dim3(nwg), blk, 0, s, p);
   else
-    hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, WM, WN, NS, A_DUAL, 0, 16, BK, 0, -1, 2, ER>), dim3(nwg), blk, 0, s, p);
+    hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, WM, WN, NS, A_DUAL, 0, 16, BK, 0, -1, 2>), dim3(nwg), blk, 0, s, p);
   MEC_LAUNCH_CHECK();
   return 0;
 }
@@ -887,15 +866,14 @@ template <int BM, int BN, int WM, int WN, int NS, int MF, int BK, int ACT>
 static int launch_cfg_act(const GemmParams& p, hipStream_t s, int nwg, dim3 blk) {
   if (p.split == 2) {  // split-f16 operands, K-interleaved terms (16x16x32 tiles only)
     if constexpr (MF == 16 && BK == 32 && 4 * (BM + BN) * BK * NS <= 160 * 1024) {
-      // ER: the early-restage schedule of the 2-stage tiles (opt().gemm_x3_restage; same bits)
-      if (NS == 1 ||
-          (NS == 2 && (opt().gemm_x3_restage == 1 || (opt().gemm_x3_restage == 2 && p.amode != A_PLAIN))))
-        return launch_x3i<BM, BN, WM, WN, NS, BK, 1>(p, s, nwg, blk);
-      return launch_x3i<BM, BN, WM, WN, NS, BK, 0>(p, s, nwg, blk);
+      return launch_x3i<BM, BN, WM, WN, NS, BK>(p, s, nwg, blk);
     } else {
       set_error("gemm_glds: interleaved split operands need a 16x16x32 tile with 32-deep stages (tiles 7xxxx)");
       return -1;
     }
+  } else if constexpr (NS == 1) {
+    set_error("gemm_glds: the one-stage tile (72128) takes interleaved split operands only");
+    return -1;
   } else if (p.split) {  // split-f16 operands (fp32x3 path): three K passes, runtime activation
     if (BM * BN <= 128 * 128 && opt().gemm_prefetch_r && p.amode == A_PLAIN && p.R && p.r_lo && p.K <= 512) {
       // split identity residual of ResNet's conv3 GEMMs, both planes prefetched (PRE = 3)
@@ -929,45 +907,38 @@ static int launch_cfg(const GemmParams& p0, hipStream_t s) {
   p.group_m = opt().gemm_glds_group_m;
   const int nwg = ((p.M + BM - 1) / BM) * (p.N / BN);
   const dim3 blk(64 * WM * WN);
-  // split tiles whose stages leave room for a second workgroup per CU (72128: one 48-KB stage; 71128 /
-  // 71064: 2 x 32 / 2 x 24 KB): the first pass's second workgroups (blocks 256..511) start late
-  p.late_dma = p.split ? opt().gemm_x3_late_dma : 0;
-  p.x3_prio = p.split ? opt().gemm_x3_prio : 0;
-  if (p.split && opt().gemm_x3_stagger && NS * (BM + BN) * BK * 4 <= 80 * 1024 && nwg > 256) {
-    p.stagger = opt().gemm_x3_stagger * 100;
-    p.stagger_lo = 256;
-    p.stagger_hi = 512;
-  }
 #ifdef MEC_PROBES
   // the K-interleaved split tile (the fp32x3 FFN1 roofline kernel) with no operand loads inside its K loop
   // (gemm_debug 1: MFMA + LDS fragment reads + epilogue only, so its time against the real kernel's prices
   // the loads) or with no epilogue (gemm_debug 2: prices the epilogue)
   // (gemm_debug 3: the epilogue without its stores; 6: with a plain (no GELU) epilogue -- prices the GELU)
-  if ((opt().gemm_debug == 1 || opt().gemm_debug == 2 || opt().gemm_debug == 3 || opt().gemm_debug == 6) &&
-      p.split == 2 && BN == 256 && BM == 256 && p.amode == A_PLAIN) {
-    if constexpr (MF == 16 && BK == 32 && 4 * (BM + BN) * BK * NS <= 160 * 1024) {
-      if (opt().gemm_debug == 1)
-        hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, WM, WN, NS, A_PLAIN, 1, MF, BK, 0, -1, 2>), dim3(nwg), blk, 0, s, p);
-      else if (opt().gemm_debug == 2)
-        hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, WM, WN, NS, A_PLAIN, 2, MF, BK, 0, -1, 2>), dim3(nwg), blk, 0, s, p);
-      else if (opt().gemm_debug == 3)
-        hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, WM, WN, NS, A_PLAIN, 3, MF, BK, 0, -1, 2>), dim3(nwg), blk, 0, s, p);
-      else {
-        GemmParams q = p;
-        q.act = ACT_NONE;
-        hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, WM, WN, NS, A_PLAIN, 0, MF, BK, 0, -1, 2>), dim3(nwg), blk, 0, s, q);
+  if constexpr (BM == 256 && BN == 256) {  // the 256 x 256 tiles only
+    if ((opt().gemm_debug == 1 || opt().gemm_debug == 2 || opt().gemm_debug == 3 || opt().gemm_debug == 6) &&
+        p.split == 2 && p.amode == A_PLAIN) {
+      if constexpr (MF == 16 && BK == 32 && 4 * (BM + BN) * BK * NS <= 160 * 1024) {
+        if (opt().gemm_debug == 1)
+          hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, WM, WN, NS, A_PLAIN, 1, MF, BK, 0, -1, 2>), dim3(nwg), blk, 0, s, p);
+        else if (opt().gemm_debug == 2)
+          hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, WM, WN, NS, A_PLAIN, 2, MF, BK, 0, -1, 2>), dim3(nwg), blk, 0, s, p);
+        else if (opt().gemm_debug == 3)
+          hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, WM, WN, NS, A_PLAIN, 3, MF, BK, 0, -1, 2>), dim3(nwg), blk, 0, s, p);
+        else {
+          GemmParams q = p;
+          q.act = ACT_NONE;
+          hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, WM, WN, NS, A_PLAIN, 0, MF, BK, 0, -1, 2>), dim3(nwg), blk, 0, s, q);
+        }
       }
+      MEC_LAUNCH_CHECK();
+      return 0;
     }
-    MEC_LAUNCH_CHECK();
-    return 0;
-  }
-  if (opt().gemm_debug && BN == 256 && BM == 256 && p.amode == A_PLAIN) {
-    if (opt().gemm_debug == 1)
-      hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, WM, WN, NS, A_PLAIN, 1, MF, BK>), dim3(nwg), blk, 0, s, p);
-    else
-      hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, WM, WN, NS, A_PLAIN, 2, MF, BK>), dim3(nwg), blk, 0, s, p);
-    MEC_LAUNCH_CHECK();
-    return 0;
+    if (opt().gemm_debug && p.amode == A_PLAIN) {
+      if (opt().gemm_debug == 1)
+        hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, WM, WN, NS, A_PLAIN, 1, MF, BK>), dim3(nwg), blk, 0, s, p);
+      else
+        hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, WM, WN, NS, A_PLAIN, 2, MF, BK>), dim3(nwg), blk, 0, s, p);
+      MEC_LAUNCH_CHECK();
+      return 0;
+    }
   }
 #endif
   // the activation is a template argument for ReLU (ResNet) and none (BERT O-proj); others runtime
@@ -1031,7 +1002,7 @@ static int launch_bn(const GemmParams& p, hipStream_t s, int id) {
     case 71128: return launch_cfg<128, 128, 2, 2, 2, 16, 32>(p, s);
     case 71064: return launch_cfg<128, 64, 2, 2, 2, 16, 32>(p, s);
     case 70064: return launch_cfg<256, 64, 2, 2, 2, 16, 32>(p, s);
-    // 256 x 128 on 4 waves (wave tile 128 x 64) with ONE 48-KB stage (the restage schedule, ERS): two
+    // 256 x 128 on 4 waves (wave tile 128 x 64) with ONE 48-KB stage (read whole into fragments): two
     // workgroups per CU (BERT FFN2's pin outside the fused step; not an autotune candidate)
     case 72128: return launch_cfg<256, 128, 2, 2, 1, 16, 32>(p, s);
     // (measured and dropped: 4-wave 128 x 256, 256 x 128 and 256 x 256 forms, one wave per SIMD with

@@ -154,24 +154,6 @@ struct Options {
   // MFMA, a higher held clock: text 18.84 -> 17.96 ms, ResNet50 10.06 -> 9.00, fused step 28.05 ->
   // 26.19 ms at B = 256 (profiles/r03_ab_x3order_*.txt)
   int gemm_x3_order = 1;
-  // K-interleaved split tiles with a 2-stage ring (70256, 71128, 71064, 70064): early restage (a stage is
-  // refilled for k step t + 2 as soon as every wave holds step t's fragments: two steps in flight) for
-  // 1 = every A mode, 2 = the implicit-GEMM convs only (ResNet), 0 = none (the ring refilled after the barrier
-  // of step t: one step in flight); same bits. Measured (same process, B = 256): ResNet50 alone gains up to
-  // 1 % (8.79 -> 8.71 ms), but the fused step loses 0.8 % (2) / 1.7 % (1) and BERT up to 0.9 %: 0 by default
-  // (profiles/r05_ab_restage_*.txt)
-  int gemm_x3_restage = 0;
-  // split tiles with two or more workgroups per CU: the later-dispatched workgroups of the first pass start
-  // this many microseconds late (GemmParams::stagger), desynchronizing co-resident workgroups; 0 = off
-  int gemm_x3_stagger = 0;
-  // interleaved split tiles (not the restage schedule): the second wave of each SIMD issues its share of the
-  // next stage's LDS DMA after its first term group of MFMAs (1), after its second (2), or its hi planes after
-  // the first and lo planes after the second (3), not right after the step's barrier (0), so the two waves of
-  // a SIMD do not both sit in DMA issue while the matrix core idles; same bits. 1: fused fp32x3 step -1.2 /
-  // -1.6 %, BERT alone -0.7 / -1.4 %, ResNet50 neutral (profiles/r06f_ab_late_dma.txt, r06g_ab_late_dma.txt)
-  int gemm_x3_late_dma = 1;
-  // the same kernels: MFMA sections at wave priority 1, DMA issue and barriers at 0 (A/B knob)
-  int gemm_x3_prio = 0;
   // fp32x3 fused QKV + attention (one head per workgroup): every other 256-block of workgroups issues its stage
   // refill after its first (1) or second (2) MFMA term group instead of right after the barrier (0); same bits
   int qkv_x3_late_dma = 0;
@@ -279,6 +261,31 @@ struct DevBuf {
 
 int upload(DevBuf& b, const void* host, size_t bytes);
 
+// Workspace layout, stated once: a forward passes carve() a function that takes its buffers in order.
+// carve() runs it with a null base to measure, grows ws to that size, then runs it on ws (the pointers it
+// assigned are then real). Every buffer starts on a 256-byte boundary.
+struct Carver {
+  char* base;  // null: measuring
+  size_t off = 0;
+  template <class T> T* take(size_t count) {
+    off = (off + 255) & ~size_t(255);
+    T* r = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off += count * sizeof(T);
+    return r;
+  }
+};
+template <class F> int carve(DevBuf& ws, F&& layout) {
+  Carver m{nullptr};
+  layout(m);
+  MEC_TRY(ws.ensure(m.off));
+  Carver c{ws.as<char>()};
+  layout(c);
+  MEC_REQUIRE(c.off == m.off && c.off <= ws.bytes, "carve: the two passes of a workspace layout differ");
+  return 0;
+}
+
+int cu_count();  // compute units of the current device (cached per device); -1 with the error set on failure
+
 // Sequential reader over the canonical fp32 host blob (mec/synthetic.py: spec()).
 struct BlobReader {
   const float* p;
@@ -341,13 +348,6 @@ struct GemmParams {
   float cscale = 1.f;
   unsigned* ovf = nullptr;  // split output's range flag (x3_raise); launch_gemm fills in range_flag()
   long long r_lo = 0;  // != 0: the f16 residual R is a hi plane + a lo plane at R + r_lo (R = hi + lo)
-  // start stagger (opt().gemm_x3_stagger): blocks [stagger_lo, stagger_hi) -- the second resident workgroup of
-  // each CU in dispatch order -- wait `stagger` ticks of the 100-MHz realtime clock before starting, so the
-  // two workgroups sharing a CU run half a tile apart and one's epilogue (GELU, plane stores) overlaps the
-  // other's MFMAs instead of both bursting together. Speed only: no result depends on it
-  int stagger = 0, stagger_lo = 0, stagger_hi = 0;
-  int late_dma = 0;  // opt().gemm_x3_late_dma (gemm_glds_kernel, interleaved split tiles)
-  int x3_prio = 0;   // opt().gemm_x3_prio (the same kernels)
 };
 
 // conv / dual geometry (gemm.hip): what both engines require of ks, stride, pad and the extents before a

@@ -790,12 +790,8 @@ int MobileNetModel::create(const float* blob, size_t n) {
 template <int S, int TO, int CINP, int HIDP, int COUTP, bool EXPAND, bool RES, int STEM>
 static int run_block(const MbArgs& a, int B, hipStream_t s, int impl) {
   if (impl == 2) {
-    static int ncu = 0;
-    if (!ncu) {
-      int dev = 0;
-      MEC_HIP(hipGetDevice(&dev));
-      MEC_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-    }
+    const int ncu = cu_count();
+    if (ncu < 0) return -1;
     const int tpr = (a.OH + MBW_TO - 1) / MBW_TO;
     const int ntiles = B * tpr * tpr;
     const int grid = std::min((ntiles + 3) / 4, 8 * ncu);  // waves loop over the remaining tiles
@@ -1004,20 +1000,20 @@ int MobileNetModel::forward_u8(const uint8_t* img, int B, int H, int W, int C, f
   }
   const size_t per_big = (size_t)112 * 112 * 16;  // largest block output (features[1]), elements
   const size_t per_last = (size_t)49 * 1280;
-  const size_t per_img =
-      224 * 224 + (2 * per_big + per_last + pe + pd + 2 * pp) * sizeof(f16) + 1280 * sizeof(float) + 64;
-  if (ws.bytes < per_img * (size_t)B + 4096) MEC_TRY(ws.ensure(per_img * (size_t)B + 4096));
-  char* p = ws.as<char>();
-  uint8_t* resized = reinterpret_cast<uint8_t*>(p);
-  p += ((size_t)B * 224 * 224 + 255) / 256 * 256;
-  f16* X = reinterpret_cast<f16*>(p); p += (size_t)B * per_big * sizeof(f16);
-  f16* Y = reinterpret_cast<f16*>(p); p += (size_t)B * per_big * sizeof(f16);
-  f16* L = reinterpret_cast<f16*>(p); p += (size_t)B * per_last * sizeof(f16);
-  float* pooled = reinterpret_cast<float*>(p); p += ((size_t)B * 1280 * sizeof(float) + 255) / 256 * 256;
-  f16* Eb = reinterpret_cast<f16*>(p); p += (size_t)B * pe * sizeof(f16);
-  f16* Db = reinterpret_cast<f16*>(p); p += (size_t)B * pd * sizeof(f16);
-  f16* P0 = reinterpret_cast<f16*>(p); p += (size_t)B * pp * sizeof(f16);
-  f16* P1 = reinterpret_cast<f16*>(p);
+  uint8_t* resized;
+  f16 *X, *Y, *L, *Eb, *Db, *P0, *P1;
+  float* pooled;
+  MEC_TRY(carve(ws, [&](Carver& c) {
+    resized = c.take<uint8_t>((size_t)B * 224 * 224);
+    X = c.take<f16>(B * per_big);
+    Y = c.take<f16>(B * per_big);
+    L = c.take<f16>(B * per_last);
+    pooled = c.take<float>((size_t)B * 1280);
+    Eb = c.take<f16>(B * pe);
+    Db = c.take<f16>(B * pd);
+    P0 = c.take<f16>(B * pp);
+    P1 = c.take<f16>(B * pp);
+  }));
 
   const f16* Wt = wts.as<f16>();
   const float* P = prm.as<float>();

@@ -228,19 +228,18 @@ int MobileNetModel::forward_f32(const uint8_t* img, int B, int H, int W, int C, 
       h = oh;
     }
   }
-  const size_t per_img = 224 * 224 + ((size_t)12544 * MB_STEM_K + 2 * big_io + big_e + big_d + 49 * 1280 + 1280) * 4;
-  const size_t need = per_img * (size_t)B + 8192;
-  if (ws.bytes < need) MEC_TRY(ws.ensure(need));
-  char* p = ws.as<char>();
-  uint8_t* resized = reinterpret_cast<uint8_t*>(p);
-  p += ((size_t)B * 224 * 224 + 255) / 256 * 256;
-  float* A0 = reinterpret_cast<float*>(p); p += (size_t)B * 12544 * MB_STEM_K * 4;
-  float* X = reinterpret_cast<float*>(p); p += (size_t)B * big_io * 4;
-  float* Y = reinterpret_cast<float*>(p); p += (size_t)B * big_io * 4;
-  float* E = reinterpret_cast<float*>(p); p += (size_t)B * big_e * 4;
-  float* D = reinterpret_cast<float*>(p); p += (size_t)B * big_d * 4;
-  float* Lst = reinterpret_cast<float*>(p); p += (size_t)B * 49 * 1280 * 4;
-  float* pooled = reinterpret_cast<float*>(p);
+  uint8_t* resized;
+  float *A0, *X, *Y, *E, *D, *Lst, *pooled;
+  MEC_TRY(carve(ws, [&](Carver& c) {
+    resized = c.take<uint8_t>((size_t)B * 224 * 224);
+    A0 = c.take<float>((size_t)B * 12544 * MB_STEM_K);
+    X = c.take<float>(B * big_io);
+    Y = c.take<float>(B * big_io);
+    E = c.take<float>(B * big_e);
+    D = c.take<float>(B * big_d);
+    Lst = c.take<float>((size_t)B * 49 * 1280);
+    pooled = c.take<float>((size_t)B * 1280);
+  }));
 
   const float* Wt = wts32.as<float>();
   const float* P = prm.as<float>();

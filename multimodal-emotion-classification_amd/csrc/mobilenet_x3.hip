@@ -879,22 +879,21 @@ int MobileNetModel::forward_x3(const uint8_t* img, int B, int H, int W, int C, f
   }
   const size_t per_big = (size_t)112 * 112 * 16;  // largest block output (features[1]), floats
   const size_t per_last = (size_t)49 * 1280;
-  const size_t per_img = 224 * 224 + (2 * per_big + per_last + 1280) * sizeof(float) +
-                         pe * sizeof(float) + (pd + 2 * pp) * 2 * sizeof(f16);
-  const size_t need = per_img * (size_t)B + 8192;
-  if (ws.bytes < need) MEC_TRY(ws.ensure(need));
-  char* p = ws.as<char>();
-  uint8_t* resized = reinterpret_cast<uint8_t*>(p);
-  p += ((size_t)B * 224 * 224 + 255) / 256 * 256;
-  float* X = reinterpret_cast<float*>(p); p += (size_t)B * per_big * sizeof(float);
-  float* Y = reinterpret_cast<float*>(p); p += (size_t)B * per_big * sizeof(float);
-  float* Lst = reinterpret_cast<float*>(p); p += (size_t)B * per_last * sizeof(float);
-  float* pooled = reinterpret_cast<float*>(p); p += (size_t)B * 1280 * sizeof(float);
-  float* Eb = reinterpret_cast<float*>(p); p += (size_t)B * pe * sizeof(float);
   const long long dlo = (long long)B * pd, plo = (long long)B * pp;  // plane offsets (halfs)
-  f16* Db = reinterpret_cast<f16*>(p); p += (size_t)B * pd * 2 * sizeof(f16);
-  f16* P0 = reinterpret_cast<f16*>(p); p += (size_t)B * pp * 2 * sizeof(f16);
-  f16* P1 = reinterpret_cast<f16*>(p);
+  uint8_t* resized;
+  float *X, *Y, *Lst, *pooled, *Eb;
+  f16 *Db, *P0, *P1;  // hi | lo planes each
+  MEC_TRY(carve(ws, [&](Carver& c) {
+    resized = c.take<uint8_t>((size_t)B * 224 * 224);
+    X = c.take<float>(B * per_big);
+    Y = c.take<float>(B * per_big);
+    Lst = c.take<float>(B * per_last);
+    pooled = c.take<float>((size_t)B * 1280);
+    Eb = c.take<float>(B * pe);
+    Db = c.take<f16>(B * pd * 2);
+    P0 = c.take<f16>(B * pp * 2);
+    P1 = c.take<f16>(B * pp * 2);
+  }));
 
   const f16* Wt = wts.as<f16>();
   const long long wlo = (long long)x3_lo;

@@ -76,7 +76,6 @@ struct FusionModel : Model {
   DevBuf w;  // fp32, transposed Linear weights ([in][out]) + biases + LN params
   std::vector<size_t> off;  // offsets by FusionParam index
   DevBuf ws;  // split form: projected (P) and fusion-projected (T) features, f32 [B, 768] each
-  int ws_batch = 0;
   int create(const float* blob, size_t n);
   int forward(const float* sf, const float* tf, const float* imf, const float* sp, const float* tp,
               const float* ip, int B, float* logits, float* probs, float* attn_w, float* dec_w,
@@ -93,7 +92,6 @@ struct TextModel : Model {
   DevBuf prm;      // fp32 per layer: bqkv bo ln1g ln1b bi bo2 ln2g ln2b ; head: WpT bp WcT bc
   DevBuf wts32;    // fp32 path: the same GEMM weights in f32
   DevBuf ws;       // workspace
-  int ws_tokens = 0;
   int create(const float* blob, size_t n);
   int forward(const int32_t* ids, const int32_t* mask, int B, int L, float* cls, float* logits,
               float* probs, hipStream_t s);
@@ -191,7 +189,6 @@ struct ImageModel : ImageNet {
   DevBuf wts;   // f16 conv weights
   DevBuf prm;   // fp32 biases, stem weights, head
   DevBuf ws;    // workspace
-  int ws_batch = 0;
   ConvLayer stem;      // gray input (channels folded): f16 [64][64] pixel taps
   ConvLayer stem_rgb;  // RGB input: f16 [64][3*64]
   size_t stem_corr_off = 0;  // f32 [16 border classes][64] -mean/std term
@@ -240,7 +237,6 @@ struct MobileNetModel : ImageNet {
   DevBuf wts;   // f16 1x1 weights
   DevBuf prm;   // fp32 stem, depthwise weights, biases, head
   DevBuf ws;    // workspace
-  int ws_batch = 0;
   size_t stem_w_off = 0, stem_rgb_off = 0, stem_corr_off = 0;  // f32 [9][32], [3*9][32], [4 classes][32]
   std::vector<MbBlock> blocks;
   size_t last_w_off = 0, last_b_off = 0;  // features[18]: f16 [1280][320], f32 [1280]

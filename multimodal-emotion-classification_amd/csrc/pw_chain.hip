@@ -423,12 +423,8 @@ int launch_pw_chain(const f16* t2, const f16* xin, const f16* w3, const float* b
                     f16* xout, f16* t1, int M, int N2, hipStream_t s) {
   MEC_REQUIRE(M > 0 && M % PC_BM == 0, "pw_chain: rows must be a multiple of 64");
   MEC_REQUIRE(t2 && xin && w3 && b3 && w1 && b1 && xout && t1, "pw_chain: null pointer");
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    MEC_HIP(hipGetDevice(&dev));
-    MEC_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-  }
+  const int ncu = cu_count();
+  if (ncu < 0) return -1;
   const int ntiles = M / PC_BM;
   const dim3 grd(std::min(ntiles, ncu)), blk(256);
   const int form = opt().pw_chain_form ? opt().pw_chain_form : (N2 == 64 ? 1 : 2);
@@ -633,12 +629,8 @@ int launch_pw_chain_dual(const f16* t2, const f16* x0, const f16* w3ds, const fl
                          const float* b1, f16* xout, f16* t1, int M, hipStream_t s) {
   MEC_REQUIRE(M > 0 && M % PC_BM == 0, "pw_chain_dual: rows must be a multiple of 64");
   MEC_REQUIRE(t2 && x0 && w3ds && b3ds && w1 && b1 && xout && t1, "pw_chain_dual: null pointer");
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    MEC_HIP(hipGetDevice(&dev));
-    MEC_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-  }
+  const int ncu = cu_count();
+  if (ncu < 0) return -1;
   const int ntiles = M / PC_BM;
   hipLaunchKernelGGL(pw_chain_dual_kernel, dim3(std::min(ntiles, ncu)), dim3(256), 0, s, t2, x0, w3ds, b3ds, w1, b1,
                      xout, t1, ntiles);

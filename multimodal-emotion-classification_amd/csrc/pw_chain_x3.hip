@@ -353,12 +353,8 @@ int launch_pw_chain_x3(const f16* t2, const f16* xin, long long L, const f16* w3
   MEC_REQUIRE(M > 0 && M % 32 == 0, "pw_chain_x3: rows must be a multiple of 32");
   MEC_REQUIRE(t2 && xin && w3 && b3 && w1 && b1 && xout && t1 && L > 0, "pw_chain_x3: null pointer");
   MEC_REQUIRE(N2 == 64 || (N2 == 128 && !dual), "pw_chain_x3: N2 must be 64 (or 128 without the downsample)");
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    MEC_HIP(hipGetDevice(&dev));
-    MEC_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-  }
+  const int ncu = cu_count();
+  if (ncu < 0) return -1;
   PwX3Args a;
   a.a = t2; a.a2 = dual ? xin : nullptr; a.r = dual ? nullptr : xin; a.L = L;
   a.w3 = w3; a.w3_lo = w3_lo; a.os3 = os3; a.b3 = b3;

@@ -323,12 +323,8 @@ int launch_pw_seam_x3(const f16* t2, const f16* xin, long long L, const f16* w3,
   MEC_REQUIRE(M > 0, "pw_seam_x3: no rows");
   MEC_REQUIRE(t2 && xin && w3 && b3 && w1 && b1 && xout && t1 && L > 0, "pw_seam_x3: null pointer");
   MEC_REQUIRE(K3 == 128 && (N1 == 128 || N1 == 256), "pw_seam_x3: shapes K3 = 128, N1 = 128 | 256 only");
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    MEC_HIP(hipGetDevice(&dev));
-    MEC_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-  }
+  const int ncu = cu_count();
+  if (ncu < 0) return -1;
   SeamX3Args a;
   a.a = t2; a.r = xin; a.L = L;
   a.w3 = w3; a.w3_lo = w3_lo; a.os3 = os3; a.b3 = b3;

@@ -509,23 +509,20 @@ int ImageModel::forward_u8(const uint8_t* img, int B, int H, int W, int C, float
   if (prec == PREC_FP32X3) return forward_x3(img, B, H, W, C, feat, logits, probs, s);
   const size_t per_img_big = (size_t)56 * 56 * 256;  // largest NHWC activation (elements)
   const size_t per_t1 = (size_t)56 * 56 * 128, per_t2 = (size_t)56 * 56 * 64;
-  const size_t per_img = 224 * 224 + (2 * per_img_big + per_t1 + per_t2) * sizeof(f16) + 256 + 2048 * sizeof(float);
-  if (B > ws_batch) {
-    MEC_TRY(ws.ensure(per_img * (size_t)B + 4096));
-    ws_batch = B;
-  }
-  char* p = ws.as<char>();
-  uint8_t* resized = reinterpret_cast<uint8_t*>(p);
-  p += ((size_t)B * 224 * 224 + 255) / 256 * 256;
-  f16* X = reinterpret_cast<f16*>(p); p += (size_t)B * per_img_big * sizeof(f16);
-  f16* Y = reinterpret_cast<f16*>(p); p += (size_t)B * per_img_big * sizeof(f16);
+  uint8_t* resized;
+  f16 *X, *Y, *T1, *T2;
+  float* pooled;  // [B,2048]
+  MEC_TRY(carve(ws, [&](Carver& c) {
+    resized = c.take<uint8_t>((size_t)B * 224 * 224);
+    X = c.take<f16>(B * per_img_big);
+    Y = c.take<f16>(B * per_img_big);
+    T1 = c.take<f16>(B * per_t1);
+    T2 = c.take<f16>(B * per_t2);
+    pooled = c.take<float>((size_t)B * 2048);
+  }));
   // the stem output [B,56,56,64] sits in the last quarter of X: a chunk's layer-1 outputs (4x the
   // per-image stride) then never reach the stem output of a later chunk's images (resnet_chunk)
   f16* Xs = X + (size_t)3 * B * 56 * 56 * 64;
-  f16* T1 = reinterpret_cast<f16*>(p); p += (size_t)B * per_t1 * sizeof(f16);
-  f16* T2 = reinterpret_cast<f16*>(p);
-  p += (size_t)B * per_t2 * sizeof(f16);
-  float* pooled = reinterpret_cast<float*>(p);  // [B,2048]
 
   const f16* Wt = wts.as<f16>();
   const float* P = prm.as<float>();
@@ -537,12 +534,8 @@ int ImageModel::forward_u8(const uint8_t* img, int B, int H, int W, int C, float
   {  // fused stem conv 7x7/2 + BN + ReLU + maxpool 3x3/2 -> X [B,56,56,64]
     const ConvLayer& st = C == 3 ? stem_rgb : stem;
     MEC_TRY(prof.begin(TAG_RESNET_STEM, s));
-    static int ncu = 0;
-    if (!ncu) {
-      int dev = 0;
-      MEC_HIP(hipGetDevice(&dev));
-      MEC_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-    }
+    const int ncu = cu_count();
+    if (ncu < 0) return -1;
     const int ntiles = B * 49;  // two resident workgroups per CU (VGPR-bound)
     const dim3 sg(std::min(ntiles, 2 * ncu)), sb(256);
     const f16* sw = Wt + st.w_off;

@@ -606,19 +606,18 @@ int ImageModel::forward_f32(const uint8_t* img, int B, int H, int W, int C, floa
   // per image (floats): im2col 12544 x 160; X, Y, DS 56*56*256 (also the 112*112*64 stem
   // output); T1 56*56*128; T2 56*56*64; pooled 2048
   const size_t big = (size_t)56 * 56 * 256;
-  const size_t per_img = 224 * 224 + ((size_t)12544 * STEM_K + 3 * big + 56 * 56 * 128 + 56 * 56 * 64 + 2048) * 4;
-  const size_t need = per_img * (size_t)B + 8192;
-  if (ws.bytes < need) MEC_TRY(ws.ensure(need));
-  char* p = ws.as<char>();
-  uint8_t* resized = reinterpret_cast<uint8_t*>(p);
-  p += ((size_t)B * 224 * 224 + 255) / 256 * 256;
-  float* A0 = reinterpret_cast<float*>(p); p += (size_t)B * 12544 * STEM_K * 4;
-  float* X = reinterpret_cast<float*>(p); p += (size_t)B * big * 4;
-  float* Y = reinterpret_cast<float*>(p); p += (size_t)B * big * 4;
-  float* DS = reinterpret_cast<float*>(p); p += (size_t)B * big * 4;
-  float* T1 = reinterpret_cast<float*>(p); p += (size_t)B * 56 * 56 * 128 * 4;
-  float* T2 = reinterpret_cast<float*>(p); p += (size_t)B * 56 * 56 * 64 * 4;
-  float* pooled = reinterpret_cast<float*>(p);
+  uint8_t* resized;
+  float *A0, *X, *Y, *DS, *T1, *T2, *pooled;
+  MEC_TRY(carve(ws, [&](Carver& c) {
+    resized = c.take<uint8_t>((size_t)B * 224 * 224);
+    A0 = c.take<float>((size_t)B * 12544 * STEM_K);
+    X = c.take<float>(B * big);
+    Y = c.take<float>(B * big);
+    DS = c.take<float>(B * big);
+    T1 = c.take<float>((size_t)B * 56 * 56 * 128);
+    T2 = c.take<float>((size_t)B * 56 * 56 * 64);
+    pooled = c.take<float>((size_t)B * 2048);
+  }));
 
   const float* Wt = wts32.as<float>();
   const float* P = prm.as<float>();
@@ -631,12 +630,8 @@ int ImageModel::forward_f32(const uint8_t* img, int B, int H, int W, int C, floa
   }
   MEC_TRY(prof.begin(TAG_RESNET_STEM, s));
   if (Cin == 1 && opt().stem_gray_f32) {  // conv + BN + ReLU + maxpool in one kernel -> X
-    static int ncu = 0;
-    if (!ncu) {
-      int dev = 0;
-      MEC_HIP(hipGetDevice(&dev));
-      MEC_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-    }
+    const int ncu = cu_count();
+    if (ncu < 0) return -1;
     const int ntiles = B * 49;
     hipLaunchKernelGGL(stem_pool_gray_f32_kernel, dim3(std::min(ntiles, ncu)), dim3(512), 0, s, stem_in, ntiles,
                        Wt + stem_gray32_off, P + stem.b_off, X);
@@ -714,16 +709,16 @@ int ImageModel::forward_x3(const uint8_t* img, int B, int H, int W, int C, float
   // (56*56*128), T2 (56*56*64) halfs, then the lo half (same layout)
   const size_t big = (size_t)56 * 56 * 256, t1n = (size_t)56 * 56 * 128, t2n = (size_t)56 * 56 * 64;
   const size_t arena_img = 2 * big + t1n + t2n;  // halfs per image per half-arena
-  const size_t per_img = 224 * 224 + ((size_t)12544 * STEM_K + (size_t)56 * 56 * 64 + 2048) * 4 + arena_img * 2 * 2;
-  const size_t need = per_img * (size_t)B + 8192;
-  if (ws.bytes < need) MEC_TRY(ws.ensure(need));
-  char* p = ws.as<char>();
-  uint8_t* resized = reinterpret_cast<uint8_t*>(p);
-  p += ((size_t)B * 224 * 224 + 255) / 256 * 256;
-  float* A0 = reinterpret_cast<float*>(p); p += (size_t)B * 12544 * STEM_K * 4;
-  float* S32 = reinterpret_cast<float*>(p); p += (size_t)B * 56 * 56 * 64 * 4;
-  float* pooled = reinterpret_cast<float*>(p); p += (size_t)B * 2048 * 4;
-  f16* arena = reinterpret_cast<f16*>(p);
+  uint8_t* resized;
+  float *A0, *S32, *pooled;
+  f16* arena;  // hi half, then lo half
+  MEC_TRY(carve(ws, [&](Carver& c) {
+    resized = c.take<uint8_t>((size_t)B * 224 * 224);
+    A0 = c.take<float>((size_t)B * 12544 * STEM_K);
+    S32 = c.take<float>((size_t)B * 56 * 56 * 64);
+    pooled = c.take<float>((size_t)B * 2048);
+    arena = c.take<f16>(B * arena_img * 2);
+  }));
   const long long L = (long long)B * arena_img;  // lo plane = hi plane + L, for every activation
   f16* X = arena;
   f16* Y = X + (size_t)B * big;
@@ -748,12 +743,8 @@ int ImageModel::forward_x3(const uint8_t* img, int B, int H, int W, int C, float
   // stem -> S32 f32 [B,56,56,64] (the fp32 path's kernels), then split into X's planes
   MEC_TRY(prof.begin(TAG_RESNET_STEM, s));
   if (Cin == 1 && opt().stem_gray_f32) {  // conv + BN + ReLU + pool on split weights -> X's planes
-    static int ncu = 0;
-    if (!ncu) {
-      int dev = 0;
-      MEC_HIP(hipGetDevice(&dev));
-      MEC_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-    }
+    const int ncu = cu_count();
+    if (ncu < 0) return -1;
     const int ntiles = B * 49;
     hipLaunchKernelGGL(stem_pool_gray_x3_kernel, dim3(std::min(ntiles, ncu)), dim3(512), 0, s, stem_in, ntiles,
                        Wt32 + stem_gray32_off, stem_x3_up, std::ldexp(stem.x3_scale, stem.x3_s), P + stem.x3b_off, Xs, L,

@@ -1,5 +1,6 @@
 // Runtime plumbing: thread-local error string, device buffers, hipEvent timing hook.
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 
@@ -52,6 +53,20 @@ void DevBuf::release() {
   if (p) (void)hipFree(p);
   p = nullptr;
   bytes = 0;
+}
+
+int cu_count() {
+  constexpr int kDevs = 64;
+  static std::atomic<int> cache[kDevs];  // 0 = not asked yet
+  int dev = 0;
+  MEC_HIP(hipGetDevice(&dev));
+  int n = dev < kDevs ? cache[dev].load(std::memory_order_relaxed) : 0;
+  if (!n) {
+    MEC_HIP(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
+    MEC_REQUIRE(n > 0, "cu_count: the device reports no compute units");
+    if (dev < kDevs) cache[dev].store(n, std::memory_order_relaxed);
+  }
+  return n;
 }
 
 int upload(DevBuf& b, const void* host, size_t bytes) {

@@ -722,12 +722,11 @@ int FusionModel::forward(const float* sf, const float* tf, const float* imf, con
   const int R = opt().fusion_r;
   const dim3 grid((B + R - 1) / R), blk(SF_THREADS);
   if (opt().fusion_split) {
-    if (B > ws_batch) {
-      MEC_TRY(ws.ensure((size_t)B * 768 * 2 * sizeof(float)));
-      ws_batch = B;
-    }
-    float* Pg = ws.as<float>();
-    float* Tg = Pg + (size_t)B * 768;
+    float *Pg, *Tg;
+    MEC_TRY(carve(ws, [&](Carver& c) {
+      Pg = c.take<float>((size_t)B * 768);
+      Tg = c.take<float>((size_t)B * 768);
+    }));
     switch (R) {
       case 1: launch_fusion_split<1>(p, sf, tf, imf, sp, tp, ip, B, Pg, Tg, logits, probs, attn_w, dec_w, s); break;
       case 4: launch_fusion_split<4>(p, sf, tf, imf, sp, tp, ip, B, Pg, Tg, logits, probs, attn_w, dec_w, s); break;

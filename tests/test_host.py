@@ -76,9 +76,13 @@ def test_model_option_and_query_need_a_handle():
 
 def test_removed_knobs_are_unknown():
     """The measured-slower opt-in paths of round 2 (register-staged GEMM engine, fused
-    bottleneck tail, O-proj + LN kernel, one-kernel speech DNN) are gone from the library."""
+    bottleneck tail, O-proj + LN kernel, one-kernel speech DNN) are gone from the library, and so are
+    the split GEMM's fp32x3 schedule A/B knobs of rounds 5-6 (early restage, start stagger, MFMA wave
+    priority and the late-DMA variants): the split tiles now always run what was gemm_x3_late_dma 1,
+    the rest off."""
     lib = _lib.load()
-    for k in (b'gemm_impl', b'resnet_fused_tail', b'bert_oproj_ln', b'speech_impl'):
+    for k in (b'gemm_impl', b'resnet_fused_tail', b'bert_oproj_ln', b'speech_impl', b'gemm_x3_restage',
+              b'gemm_x3_stagger', b'gemm_x3_prio', b'gemm_x3_late_dma'):
         assert lib.mec_set_option(k, 0) == -1 and b'unknown' in lib.mec_last_error().lower(), k
 
 
