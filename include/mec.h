@@ -25,11 +25,14 @@ extern "C" {
 
 typedef struct mec_model mec_model;
 
-enum { MEC_SPEECH = 0, MEC_TEXT = 1, MEC_IMAGE = 2, MEC_FUSION = 3, MEC_IMAGE_MBV2 = 4, MEC_AUDIO = 5 };
+enum { MEC_SPEECH = 0, MEC_TEXT = 1, MEC_IMAGE = 2, MEC_FUSION = 3, MEC_IMAGE_MBV2 = 4, MEC_AUDIO = 5, MEC_TEXT_LSTM = 6 };
 /* MEC_IMAGE is the reference's ResNet50 image model (inference/image_inference.py:55-65);
  * MEC_IMAGE_MBV2 the same head on a torchvision mobilenet_v2 backbone (README.md:13 names
  * MobileNetV2; blob = state_dict order of mec/synthetic.py:image_mbv2_spec). Both kinds are
- * accepted by mec_image_fwd / mec_image_fwd_u8. */
+ * accepted by mec_image_fwd / mec_image_fwd_u8.
+ * MEC_TEXT_LSTM is the reference's second text model, the Keras BiLSTM of
+ * model_training/train_lstm_text_model.py:96-120 (blob = Keras layer order of
+ * mec/synthetic.py:text_lstm_spec; the embedding has 10000 rows, smaller trained vocabularies zero-padded). */
 
 /* Version / diagnostics. */
 const char* mec_version(void);
@@ -44,7 +47,8 @@ long long mec_blob_size(int kind);
  *   text    BertForSequenceClassification.from_pretrained inference/text_inference.py:40-43
  *   image   _build_model + load_state_dict               inference/image_inference.py:35-40
  *           (MEC_IMAGE_MBV2: the same with base = mobilenet_v2, base.classifier = the head)
- *   fusion  _build_fusion_model + load_state_dict        inference/multimodal_fusion.py:43-56 */
+ *   fusion  _build_fusion_model + load_state_dict        inference/multimodal_fusion.py:43-56
+ *   text (BiLSTM)  tf.keras load_model                   inference/text_lstm_inference.py:35-36 */
 int mec_create(int kind, const float* host_blob, size_t n, int device, mec_model** out);
 
 /* Arithmetic of a handle. MEC_PREC_F16 (mec_create's default, the fast path): BERT and the
@@ -65,7 +69,7 @@ int mec_create(int kind, const float* host_blob, size_t n, int device, mec_model
  * over a 6-sigma estimate), so the planes hold 22 significant bits for the tensor's whole working
  * range (INTEGRATION.md "fp32x3 envelope"). A plane value at |x 2^s| >= 65520 (activations far above
  * what the BN parameters predict) or a NaN / inf raises the handle's range flag and mec_model_check
- * fails. Speech, fusion and audio handles are fp32 at every setting. */
+ * fails. Speech, fusion, audio and BiLSTM text handles are fp32 at every setting. */
 enum { MEC_PREC_F16 = 0, MEC_PREC_FP32 = 1, MEC_PREC_FP32X3 = 2 };
 int mec_create_ex(int kind, const float* host_blob, size_t n, int device, int precision, mec_model** out);
 /* mec_create_ex with this handle's own knobs, "key=value[,key=value...]" (the keys of mec_set_option),
@@ -99,6 +103,17 @@ int mec_speech_fwd(mec_model* m, const float* x, int B, float* feat, float* logi
  *   inference/text_inference.py:87-94, :119-128. */
 int mec_text_fwd(mec_model* m, const int32_t* ids, const int32_t* mask, int B, int L, float* cls,
                  float* logits, float* probs, void* stream);
+
+/* BiLSTM text model (MEC_TEXT_LSTM handle). ids int32[B,L] with L == 128, post-padded and
+ * post-truncated with id 0 (pad_sequences(padding='post', truncating='post')); the embedding has no
+ * mask_zero, so pad positions run through the LSTMs like any token. ids outside [0, 10000) are clamped.
+ * Outputs feat f32[B,64] (the Dense-64 ReLU) or NULL, logits f32[B,7] or NULL, probs f32[B,7].
+ * B == 0 returns 0 and launches nothing; a null handle, a handle of another kind or L != 128 returns -1
+ * before any launch. fp32 throughout (no f16 anywhere), a row's bits independent of B and of its
+ * position in the batch. Replaces FastTextEmotionPredictor.predict / predict_batch model arithmetic
+ *   inference/text_lstm_inference.py:66, :106. */
+int mec_text_lstm_fwd(mec_model* m, const int32_t* ids, int B, int L, float* feat, float* logits, float* probs,
+                      void* stream);
 
 /* ResNet50 image encoder + head. gray: u8[B,48,48]; the PIL RGB/resize/ToTensor/Normalize
  * transform runs on the GPU. Outputs feat f32[B,512] (fc[2]), logits, probs f32[B,7].
@@ -162,6 +177,14 @@ int mec_gemm_f32(const float* A, const float* B, const float* bias, const float*
 /* Implicit-GEMM conv on NHWC f32 (C % 32 == 0), same geometry as mec_conv_f16. */
 int mec_conv_f32(const float* x, const float* w, const float* bias, const float* R, float* y, int n, int H, int W,
                  int C, int Cout, int ks, int stride, int pad, int act, void* stream);
+/* One LSTM direction (Keras semantics, gate columns i | f | c | o, h0 = c0 = 0) over hoisted input
+ * projections: xz f32[B,L,4u] = x.W + b, U f32[u,4u] the recurrent kernel; per step z = xz_t + h.U,
+ * c = sigmoid(z_f) c + sigmoid(z_i) tanh(z_c), h = sigmoid(z_o) tanh(c). reverse = 1 walks t = L-1..0
+ * (y_seq stays in time order). y_seq f32[B,L,u] and/or h_last f32[B,u] (the h after the last step walked);
+ * either may be NULL, not both. units 64 or 128 and L >= 1; anything else returns -1 without a launch;
+ * B == 0 returns 0. The BiLSTM model's recurrent kernel ("lstm_rows" applies). */
+int mec_lstm_seq_f32(const float* xz, const float* U, int B, int L, int units, int reverse, float* y_seq,
+                     float* h_last, void* stream);
 /* Conv geometry (mec_conv_f16, mec_conv_f32, mec_gemm_ex): n >= 1, ks >= 1, stride >= 1, pad >= 0 and
  * ks <= H + 2 pad, ks <= W + 2 pad (OH, OW >= 1); anything else returns -1 before any launch. */
 
@@ -272,6 +295,8 @@ int mec_gemm_ex(const mec_gemm_args* a, void* stream);
  *   "mbv2_impl" [0]|1|2    MobileNetV2 block form: 0 = time both per block shape, 1 = workgroup, 2 = wave
  *   "fusion_r" 1|2|[4]     samples per fusion workgroup
  *   "fusion_split" 0|[1]   fusion as 3 launches (per-modality projection, cross-attention, head)
+ *   "lstm_rows" 1|[2]|4    BiLSTM recurrent kernel: rows of one direction per workgroup, sharing its
+ *                          register-resident recurrent weights (same bits for every value)
  * Probe values, which skip work to time a kernel's parts and return WRONG results, exist only
  * in the -DMEC_PROBES build (libmec_hip_probes.so, `make probes`; tools/ only): "gemm_debug"
  * 1..5, "conv3x3_debug" / "stem_debug" 1|2|4|7, "bert_qkv_attn" 2|3,

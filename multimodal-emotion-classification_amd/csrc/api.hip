@@ -62,6 +62,12 @@ size_t blob_floats(int kind) {
       return s;
     }
     case KIND_AUDIO: return 5;  // [sample_rate, n_fft, hop, n_mels, n_mfcc]
+    case KIND_TEXT_LSTM: {
+      size_t s = (size_t)LstmTextModel::kVocab * 128;
+      s += 2 * ((size_t)128 * 512 + 128 * 512 + 512);  // Bidirectional(LSTM 128): kernel, recurrent_kernel, bias
+      s += 2 * ((size_t)256 * 256 + 64 * 256 + 256);   // Bidirectional(LSTM 64)
+      return s + 128 * 128 + 128 + 128 * 64 + 64 + 64 * 7 + 7;
+    }
     default: return 0;
   }
 }
@@ -160,18 +166,19 @@ int mec_create_opt(int kind, const float* host_blob, size_t n, int device, int p
     Model* impl = nullptr;
     int rc = -1;
     switch (kind) {
-      // speech and fusion are fp32 at either precision
+      // speech, fusion, audio and the BiLSTM are fp32 at every precision
       case KIND_SPEECH: { auto* p = new SpeechModel(); impl = p; p->opts = o; rc = p->create(host_blob, n); break; }
       case KIND_TEXT: { auto* p = new TextModel(); p->prec = precision; impl = p; p->opts = o; rc = p->create(host_blob, n); break; }
       case KIND_IMAGE: { auto* p = new ImageModel(); p->prec = precision; impl = p; p->opts = o; rc = p->create(host_blob, n); break; }
       case KIND_FUSION: { auto* p = new FusionModel(); impl = p; p->opts = o; rc = p->create(host_blob, n); break; }
       case KIND_IMAGE_MBV2: { auto* p = new MobileNetModel(); p->prec = precision; impl = p; p->opts = o; rc = p->create(host_blob, n); break; }
       case KIND_AUDIO: { auto* p = new AudioModel(); impl = p; p->opts = o; rc = p->create(host_blob, n); break; }
+      case KIND_TEXT_LSTM: { auto* p = new LstmTextModel(); impl = p; p->opts = o; rc = p->create(host_blob, n); break; }
     }
     if (rc != 0) { delete impl; return -1; }
     impl->kind = kind;
     impl->device = device;
-    impl->prec = (kind == KIND_SPEECH || kind == KIND_FUSION || kind == KIND_AUDIO) ? MEC_PREC_FP32 : precision;
+    impl->prec = (kind == KIND_SPEECH || kind == KIND_FUSION || kind == KIND_AUDIO || kind == KIND_TEXT_LSTM) ? MEC_PREC_FP32 : precision;
     if (impl->prec == PREC_FP32X3 && impl->alloc_range_flag() != 0) { delete impl; return -1; }
     if (impl->prec == PREC_FP32X3)
       impl->x3_report = "x3_headroom=" + std::to_string(o.x3_headroom) + " x3_plane_scale=" +
@@ -251,6 +258,21 @@ int mec_audio_fwd(mec_model* m, const float* wave, int B, int n_samples, float* 
     OptScope sc(&p->opts, &p->tune, p->range_dev);
     return p->forward(wave, B, n_samples, feat, tuning, S(stream));
   })
+}
+
+int mec_text_lstm_fwd(mec_model* m, const int32_t* ids, int B, int L, float* feat, float* logits, float* probs,
+                      void* stream) {
+  API_GUARD({
+    auto* p = as<LstmTextModel>(m, KIND_TEXT_LSTM);
+    if (!p) return -1;
+    OptScope sc(&p->opts, &p->tune, p->range_dev);
+    return p->forward(ids, B, L, feat, logits, probs, S(stream));
+  })
+}
+
+int mec_lstm_seq_f32(const float* xz, const float* U, int B, int L, int units, int reverse, float* y_seq,
+                     float* h_last, void* stream) {
+  API_GUARD({ return lstm_seq_f32(xz, U, B, L, units, reverse, y_seq, h_last, S(stream)); })
 }
 
 int mec_fuse_weighted(const float* s, const float* t, const float* i, int B, double* out, void* stream) {
@@ -352,6 +374,7 @@ int set_option(Options& o, const std::string& k, int value) {
     o.gemm_glds_group_m = value;
     return 0;
   }
+  if (k == "lstm_rows" && (value == 1 || value == 2 || value == 4)) { o.lstm_rows = value; return 0; }
   if (k == "fusion_split" && (value == 0 || value == 1)) { o.fusion_split = value; return 0; }
   if (k == "speech_spin_limit" && (value == -1 || (probe && value >= 0))) { o.speech_spin_limit = value; return 0; }
   if (k == "gemm_debug" && (value == 0 || (probe && value >= 1 && value <= 6))) { o.gemm_debug = value; return 0; }

@@ -61,7 +61,11 @@ enum KernelTag : int {
   TAG_MBV2_BLOCK = 12,
   TAG_MBV2_LAST = 13,
   TAG_AUDIO = 14,
-  TAG_COUNT = 15,
+  TAG_COUNT = 15,  // bound of the per-tag option arrays (gemm_bn_tag ...); the tags below are timing-only
+  TAG_LSTM_PROJ = 16,
+  TAG_LSTM_REC1 = 17,
+  TAG_LSTM_REC2 = 18,
+  TAG_LSTM_HEAD = 19,
 };
 
 // Tuning knobs (mec_set_option / mec_model_set_option, include/mec.h). Every model handle
@@ -173,6 +177,9 @@ struct Options {
   // max(|x|, 1) 1.21e-7 against float64, the correctly rounded erf's 1.06e-7), 0 = libm erff
   int gelu_x3 = 1;
   int fusion_r = 4;         // samples per fusion workgroup
+  // BiLSTM recurrent kernel (text_lstm.hip): rows of one direction per workgroup (1 | 2 | 4), which share
+  // the workgroup's register-resident recurrent weights; same bits at every value
+  int lstm_rows = 2;
   int fusion_split = 1;     // fusion as 3 launches
   int gemm_debug = 0, conv3x3_debug = 0, stem_debug = 0, audio_debug = 0, speech_debug = 0;  // probe builds only
   int speech_spin_limit = -1;  // probe builds only: speech_flow_kernel wait limit (forces expired waits)

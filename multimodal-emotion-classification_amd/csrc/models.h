@@ -6,7 +6,7 @@
 
 namespace mec {
 
-enum ModelKind : int { KIND_SPEECH = 0, KIND_TEXT = 1, KIND_IMAGE = 2, KIND_FUSION = 3, KIND_IMAGE_MBV2 = 4, KIND_AUDIO = 5 };
+enum ModelKind : int { KIND_SPEECH = 0, KIND_TEXT = 1, KIND_IMAGE = 2, KIND_FUSION = 3, KIND_IMAGE_MBV2 = 4, KIND_AUDIO = 5, KIND_TEXT_LSTM = 6 };
 
 size_t blob_floats(int kind);
 
@@ -152,6 +152,23 @@ float split_planes(const float* w, size_t n, f16* hi, f16* lo);
 // Clamped to [-40, 40]; 0 for a zero or non-finite bound. Host code (runtime.hip).
 int activation_exp(double bound, double target);
 constexpr double kX3BoundTarget = 32768.0, kX3EstimateTarget = 1024.0;
+
+// ---------------------------------------------------------------- BiLSTM text model (text_lstm.hip)
+// fp32 at every precision setting. w: layer 1's projected table Emb.W + b [10000][1024] (forward | backward
+// gates, built at creation), the recurrent kernels of both layers, layer 2's input projection as the fp32
+// GEMM's B operand, the dense head (Keras kernels [in][out]).
+struct LstmTextModel : Model {
+  static constexpr int kVocab = 10000;  // train_lstm_text_model.py:171 caps vocab_size here; loaders zero-pad
+  DevBuf w, ws;
+  size_t off_table = 0, off_u1[2] = {}, off_w2 = 0, off_b2 = 0, off_u2[2] = {}, off_dw[3] = {}, off_db[3] = {};
+  int create(const float* blob, size_t n);
+  // ids int32 [B, L = 128] (post-padded with 0; pads run through the LSTMs like any token) -> feat f32 [B, 64]
+  // (Dense-64 ReLU) or null, logits f32 [B, 7] or null, probs f32 [B, 7]
+  int forward(const int32_t* ids, int B, int L, float* feat, float* logits, float* probs, hipStream_t s);
+};
+// One LSTM direction over precomputed gate pre-activations (mec_lstm_seq_f32)
+int lstm_seq_f32(const float* xz, const float* U, int B, int L, int units, int reverse, float* y_seq, float* h_last,
+                 hipStream_t s);
 
 // ---------------------------------------------------------------- image encoders
 // Both backbones take the same u8 inputs and produce the same (512-d feature, logits, probs).

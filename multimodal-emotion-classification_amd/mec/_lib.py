@@ -53,6 +53,8 @@ SIGNATURES = {
     'mec_image_fwd': (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
     'mec_image_fwd_u8': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     'mec_fusion_fwd': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'mec_text_lstm_fwd': (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
+    'mec_lstm_seq_f32': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
     'mec_audio_fwd': (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp]),
     'mec_fuse_weighted': (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_vp]),
     'mec_fuse_weighted_f64': (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_vp]),
@@ -80,7 +82,8 @@ SIGNATURES = {
 # Kernel tags for mec_prof_enable (csrc/mec_common.h KernelTag).
 TAGS = {'bert_qkv': 1, 'bert_attn': 2, 'bert_oproj': 3, 'bert_ffn1': 4, 'bert_ffn2': 5, 'bert_ln': 6,
         'resnet_conv3x3': 7, 'resnet_conv1x1': 8, 'resnet_stem': 9, 'speech': 10, 'fusion': 11,
-        'mbv2_blocks': 12, 'mbv2_last': 13, 'audio': 14}
+        'mbv2_blocks': 12, 'mbv2_last': 13, 'audio': 14,
+        'lstm_proj': 16, 'lstm_rec1': 17, 'lstm_rec2': 18, 'lstm_head': 19}
 
 
 # Handle precision (include/mec.h MEC_PREC_*): 'f16' = f16 MFMA operands with fp32

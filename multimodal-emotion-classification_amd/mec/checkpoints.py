@@ -16,6 +16,11 @@ image_inference.py:105-106, multimodal_fusion.py:204-205). Order of precedence:
                multimodal_fusion.py:41-54, train_fusion_model.py:609-618
        speech  a Keras .h5 needs h5py/TensorFlow (absent): use speech_weights.npz, written by
                an offline converter (names = synthetic.speech_spec()), see INTEGRATION.md.
+       text_lstm  the Keras BiLSTM .h5 at TEXT_MODEL_PATH likewise: text_lstm_weights.npz beside it
+               (tools/convert_text_lstm_h5.py; names = synthetic.text_lstm_spec(), an embedding
+               trained with fewer than 10000 rows is zero-padded), text_lstm_inference.py:32-36.
+               Its tokenizer is text_lstm_tokenizer.json in the same directory (lstm_tokenizer_path);
+               the reference's pickled tokenizer is never read.
 Checkpoints are read only with loaders that execute nothing from the file
 (safetensors, torch.load(weights_only=True), numpy without pickles).
 """
@@ -75,7 +80,27 @@ def load_checkpoint(kind: str):
         p = os.path.join(os.path.dirname(Config.SPEECH_MODEL_PATH), 'speech_weights.npz')
         with np.load(p, allow_pickle=False) as z:
             return _conform(kind, {k: z[k] for k in z.files})
+    if kind == 'text_lstm':
+        return load_text_lstm_npz(os.path.join(os.path.dirname(Config.TEXT_MODEL_PATH), 'text_lstm_weights.npz'))
     raise ValueError(kind)
+
+
+def load_text_lstm_npz(path):
+    """text_lstm_weights.npz (tools/convert_text_lstm_h5.py) -> the canonical weight dict."""
+    with np.load(path, allow_pickle=False) as z:
+        sd = {k: z[k] for k in z.files}
+    emb = np.asarray(sd.get('embedding/embeddings', np.zeros((0, synthetic.LSTM_EMBED))), dtype=np.float32)
+    if emb.ndim == 2 and 0 < emb.shape[0] < synthetic.LSTM_VOCAB and emb.shape[1] == synthetic.LSTM_EMBED:
+        # vocab_size = min(10000, len(word_index) + 1): rows the tokenizer can never produce
+        sd['embedding/embeddings'] = np.concatenate(
+            [emb, np.zeros((synthetic.LSTM_VOCAB - emb.shape[0], emb.shape[1]), np.float32)])
+    return _conform('text_lstm', sd)
+
+
+def lstm_tokenizer_path() -> str:
+    """The BiLSTM's tokenizer as JSON (Keras Tokenizer.to_json() or a plain word -> index dict), beside
+    Config.TEXT_MODEL_PATH."""
+    return os.path.join(os.path.dirname(Config.TEXT_MODEL_PATH), 'text_lstm_tokenizer.json')
 
 
 def precision(value=None) -> str:

@@ -251,6 +251,37 @@ class TextEncoder(HipModel):
         return cls, logits, probs
 
 
+class LstmTextEncoder(HipModel):
+    """The reference's BiLSTM text model (model_training/train_lstm_text_model.py:96-120) on the HIP
+    recurrent kernels (csrc/text_lstm.hip). fp32 at every `precision` setting, like speech and fusion."""
+    kind = 'text_lstm'
+
+    VOCAB = synthetic.LSTM_VOCAB
+
+    def forward(self, ids: torch.Tensor, check_ids: bool = False):
+        """ids int32 [B,128], post-padded with 0 -> (feat [B,64], logits [B,7], probs [B,7]).
+
+        check_ids: raise ValueError for ids outside [0, 10000) (one device min/max reduction and a
+        host sync; the batched hot path skips it, and the kernel then clamps out-of-range ids)."""
+        if not isinstance(ids, torch.Tensor):
+            raise TypeError(f'ids: expected a torch.Tensor, got {type(ids).__name__}')
+        if ids.dim() != 2:
+            raise ValueError('ids: expected [B, L]')
+        B, L = ids.shape
+        if L != 128:
+            raise ValueError('ids: L must be 128 (pad_sequences maxlen, Config.MAX_TEXT_LENGTH)')
+        _check_tensor('ids', ids, torch.int32, (B, L), self.device)
+        if check_ids and B:
+            lo, hi = (int(v) for v in torch.aminmax(ids))
+            if lo < 0 or hi >= self.VOCAB:
+                raise ValueError(f'ids: token id out of range [0, {self.VOCAB}): min {lo}, max {hi}')
+        feat, logits, probs = self._empty(B, 64), self._empty(B, 7), self._empty(B, 7)
+        with self._lock:
+            _lib.check(self.lib.mec_text_lstm_fwd(self.handle, _ptr(ids), B, L, _ptr(feat), _ptr(logits), _ptr(probs),
+                                                  _stream(self.device)), 'mec_text_lstm_fwd')
+        return feat, logits, probs
+
+
 class ImageEncoder(HipModel):
     kind = 'image'
 

@@ -18,6 +18,9 @@ Tensor names/shapes follow the reference's own layouts:
   image_mbv2  the same model on torchvision mobilenet_v2 (README.md:13): `base.features`
           + a 1280->512->7 `base.classifier` head (no reference code: parity unpinned)
   fusion  MultiModalFusionModel state_dict (multimodal_fusion.py:108-154)
+  text_lstm  Keras Sequential of model_training/train_lstm_text_model.py:96-120 (Embedding,
+          two Bidirectional LSTMs as forward then backward (kernel, recurrent_kernel, bias),
+          three Dense layers), the embedding padded to 10000 rows
 """
 from __future__ import annotations
 
@@ -52,7 +55,8 @@ def randint(seed: int, name: str, shape, lo: int, hi: int) -> np.ndarray:
 
 
 # ----------------------------------------------------------------------------- specs
-# Each spec entry: (name, shape, kind, arg)  kind in {'u' (±a), 'r' (lo,hi)}
+# Each spec entry: (name, shape, kind, arg)  kind in {'u' (±a), 'r' (lo,hi), 'b' (LSTM bias [4u]: ±a, +1 on
+# the forget quarter, Keras unit_forget_bias)}
 
 SPEECH_DIMS = [56, 512, 512, 256, 128, 64]
 
@@ -229,9 +233,35 @@ def fusion_spec():
     return s
 
 
+LSTM_VOCAB, LSTM_EMBED, LSTM_UNITS, LSTM_DENSE = 10000, 128, (128, 64), (128, 64)
+LSTM_OUT_SCALE = 30.0  # output-layer scale: clear top-2 margins (tests/test_text_lstm_oracle.py checks them)
+
+
+def text_lstm_spec():
+    """Keras layer order of create_lstm_model (train_lstm_text_model.py:96-120); gate columns i | f | c | o.
+    vocab_size is min(10000, len(word_index) + 1) there (:171): the blob always has 10000 embedding rows."""
+    s = [('embedding/embeddings', (LSTM_VOCAB, LSTM_EMBED), 'u', 0.5)]
+    fin = LSTM_EMBED
+    for li, u in enumerate(LSTM_UNITS):
+        p = 'bidirectional' + ('' if li == 0 else f'_{li}')
+        for d in ('forward', 'backward'):
+            q = f'{p}/{d}_lstm/'
+            s += [(q + 'kernel', (fin, 4 * u), 'u', float(np.sqrt(6.0 / (fin + 4 * u)))),  # glorot_uniform
+                  # uniform with an orthogonal initialiser's element variance, 1 / (4 u)
+                  (q + 'recurrent_kernel', (u, 4 * u), 'u', float(np.sqrt(3.0 / (4 * u)))),
+                  (q + 'bias', (4 * u,), 'b', 0.05)]
+        fin = 2 * u
+    for name, fo in (('dense', LSTM_DENSE[0]), ('dense_1', LSTM_DENSE[1])):
+        s += [(name + '/kernel', (fin, fo), 'u', float(np.sqrt(6.0 / (fin + fo)))), (name + '/bias', (fo,), 'u', 0.05)]
+        fin = fo
+    a = LSTM_OUT_SCALE * float(np.sqrt(6.0 / (fin + NUM_CLASSES)))
+    s += [('output/kernel', (fin, NUM_CLASSES), 'u', a), ('output/bias', (NUM_CLASSES,), 'u', 0.05)]
+    return s
+
+
 SPECS = {'speech': speech_spec, 'text': text_spec, 'image': image_spec, 'fusion': fusion_spec,
-         'image_mbv2': image_mbv2_spec}
-KIND_IDS = {'speech': 0, 'text': 1, 'image': 2, 'fusion': 3, 'image_mbv2': 4}
+         'image_mbv2': image_mbv2_spec, 'text_lstm': text_lstm_spec}
+KIND_IDS = {'speech': 0, 'text': 1, 'image': 2, 'fusion': 3, 'image_mbv2': 4, 'text_lstm': 6}
 
 
 def spec(kind: str):
@@ -244,6 +274,11 @@ def _weights_cached(kind: str, seed: int):
     for name, shape, k, arg in spec(kind):
         if k == 'u':
             out[name] = uniform(seed, f'{kind}/{name}', shape, -arg, arg)
+        elif k == 'b':
+            b = uniform(seed, f'{kind}/{name}', shape, -arg, arg)
+            u = shape[0] // 4
+            b[u:2 * u] += np.float32(1.0)
+            out[name] = b
         else:
             out[name] = uniform(seed, f'{kind}/{name}', shape, arg[0], arg[1])
     return out
@@ -304,3 +339,21 @@ def text_inputs(B: int, L: int = 128, seed: int = 0, ragged: bool = False):
 def image_inputs(B: int, seed: int = 0) -> np.ndarray:
     """u8 grayscale FER2013-shaped faces [B,48,48] ~ U{0..255}."""
     return randint(seed, 'in/image', (B, 48, 48), 0, 256).astype(np.uint8)
+
+
+def text_lstm_inputs(B: int, L: int = 128, seed: int = 0, ragged: bool = False) -> np.ndarray:
+    """Token ids [B,L] int32 as pad_sequences(padding='post', truncating='post') leaves them: word
+    indices U{1..9999}, then 0 padding (no mask: pads are ordinary tokens to the model).
+    ragged=False: every row full. ragged=True: random lengths in [1, L] with row 0 full, row 1 of
+    length 1 and row 2 all padding; row 0 also carries id 9999 and two ids outside [0, 10000)
+    (the kernel clamps them as nn.Embedding-style lookups cannot)."""
+    ids = randint(seed, 'in/text_lstm/ids', (B, L), 1, LSTM_VOCAB).astype(np.int32)
+    if ragged:
+        lens = randint(seed, 'in/text_lstm/len', (B,), 1, L + 1).astype(np.int64)
+        for row, n in ((0, L), (1, 1), (2, 0)):
+            if B > row:
+                lens[row] = n
+        ids[np.arange(L)[None, :] >= lens[:, None]] = 0
+        if B > 0 and L > 7:
+            ids[0, 3], ids[0, 5], ids[0, 7] = LSTM_VOCAB - 1, LSTM_VOCAB + 5, -3
+    return ids
