@@ -104,6 +104,33 @@ int mec_speech_fwd(mec_model* m, const float* x, int B, float* feat, float* logi
 int mec_text_fwd(mec_model* m, const int32_t* ids, const int32_t* mask, int B, int L, float* cls,
                  float* logits, float* probs, void* stream);
 
+/* Sentence packing for the BERT text path: short sentences share 128-slot rows, so a batch of B
+ * sentences runs the encoder over Bp <= B rows. The plan is made on the host (where the tokenizer's
+ * lengths are) by first-fit decreasing: samples are visited by length descending, ties by ascending
+ * index; each goes to the lowest-numbered row whose free space is at least its length, at that row's
+ * fill at that moment (its off); a new row is opened when none has room.
+ * lens int32[B] on the HOST, each in [1,128]. Writes row[B], off[B] (host) and returns the number of
+ * packed rows Bp (0 for B == 0), -1 on error (null pointer, B < 0, a length outside [1,128]). Uses no
+ * GPU. No reference counterpart (the reference pads every sentence to 128, text_inference.py:81-83). */
+int mec_text_pack_plan(const int32_t* lens, int B, int32_t* row, int32_t* off);
+
+/* mec_text_fwd on a packed batch. ids int32[B,128] (device, the padded layout mec_text_fwd takes: a
+ * sentence's len tokens first); row/off/len int32[B] (device), a plan as above with Bp rows. Sample i's
+ * tokens occupy slots off[i] .. off[i]+len[i]-1 of row row[i]; position ids restart at 0 in every
+ * sentence and a key counts only for the queries of its own sentence (a block-diagonal attention
+ * mask), so every sample's outputs are those of mec_text_fwd with a prefix mask of len[i] ones, to the
+ * precision's rounding (the key's slot changes the MFMA summation grouping, not the terms; a plan with
+ * Bp == B and every off == 0 gives the same bits). Unused slots form a segment of their own and no
+ * output reads them. Outputs in the caller's sample order, as mec_text_fwd: cls f32[B,768], logits,
+ * probs f32[B,7]. B == 0 returns 0 without a launch. Returns -1 before any launch for a null pointer,
+ * a handle of another kind, Bp < 1 with B > 0, or Bp > B. The library TRUSTS the contents of the
+ * device-side plan (it cannot read them without a synchronization): indices are clamped to the
+ * workspace, so a plan that overlaps sentences or leaves gaps yields wrong outputs, not an error.
+ * Honours bert_qkv_attn, bert_qkv_attn_heads / bert_qkv_attn_x3_heads and bert_cls_last like
+ * mec_text_fwd; the GEMM shapes (and so the autotuned tiles) follow Bp, not B. */
+int mec_text_fwd_packed(mec_model* m, const int32_t* ids, const int32_t* row, const int32_t* off,
+                        const int32_t* len, int B, int Bp, float* cls, float* logits, float* probs, void* stream);
+
 /* BiLSTM text model (MEC_TEXT_LSTM handle). ids int32[B,L] with L == 128, post-padded and
  * post-truncated with id 0 (pad_sequences(padding='post', truncating='post')); the embedding has no
  * mask_zero, so pad positions run through the LSTMs like any token. ids outside [0, 10000) are clamped.

@@ -260,6 +260,41 @@ int mec_audio_fwd(mec_model* m, const float* wave, int B, int n_samples, float* 
   })
 }
 
+// First-fit decreasing over 128-slot rows: samples by length descending (ties: ascending index), each into
+// the lowest-numbered row with room, at that row's fill; a new row when none has room. Host only.
+int mec_text_pack_plan(const int32_t* lens, int B, int32_t* row, int32_t* off) {
+  API_GUARD({
+    MEC_REQUIRE(B >= 0, "mec_text_pack_plan: B < 0");
+    if (B == 0) return 0;
+    MEC_REQUIRE(lens && row && off, "mec_text_pack_plan: null pointer (lens, row and off hold B entries; lengths in [1,128])");
+    for (int i = 0; i < B; ++i)
+      MEC_REQUIRE(lens[i] >= 1 && lens[i] <= 128, "mec_text_pack_plan: every length must be in [1,128]");
+    std::vector<int> order(B);
+    for (int i = 0; i < B; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return lens[a] > lens[b]; });
+    std::vector<int> fill;
+    for (int i : order) {
+      size_t r = 0;
+      while (r < fill.size() && 128 - fill[r] < lens[i]) ++r;
+      if (r == fill.size()) fill.push_back(0);
+      row[i] = (int32_t)r;
+      off[i] = fill[r];
+      fill[r] += lens[i];
+    }
+    return (int)fill.size();
+  })
+}
+
+int mec_text_fwd_packed(mec_model* m, const int32_t* ids, const int32_t* row, const int32_t* off, const int32_t* len,
+                        int B, int Bp, float* cls, float* logits, float* probs, void* stream) {
+  API_GUARD({
+    auto* p = as<TextModel>(m, KIND_TEXT);
+    if (!p) return -1;
+    OptScope sc(&p->opts, &p->tune, p->range_dev);
+    return p->forward_packed(ids, row, off, len, B, Bp, cls, logits, probs, S(stream));
+  })
+}
+
 int mec_text_lstm_fwd(mec_model* m, const int32_t* ids, int B, int L, float* feat, float* logits, float* probs,
                       void* stream) {
   API_GUARD({

@@ -23,6 +23,7 @@
 namespace mec {
 
 constexpr int BH = 768, BI = 3072, BHEADS = 12, BDH = 64, BLAYERS = 12, BVOCAB = 30522, BMAXPOS = 512;
+constexpr int ATT_L = 128;  // the sequence length every kernel here is built for
 
 // ----------------------------------------------------------------------------- embed+LN
 // One wave per token row; each lane owns 12 of the 768 features (3 float4).
@@ -32,7 +33,10 @@ __global__ __launch_bounds__(256) void bert_embed_ln_kernel(const int32_t* __res
                                                             const float* __restrict__ type,
                                                             const float* __restrict__ g,
                                                             const float* __restrict__ b, float* h32,
-                                                            f16* h16, long long lo, float up, unsigned* flag) {
+                                                            f16* h16, long long lo, float up, unsigned* flag,
+                                                            const int32_t* __restrict__ posid) {
+  // posid (or null): the position id of every row in place of row % L (the packed path: a token's
+  // offset inside its own sentence)
   // lo != 0 (the fp32x3 path): h16 is a hi plane and h16 + lo the lo plane of y up (hi = f16(y up),
   // lo = f16(y up - hi); up = 2^s, the planes' scale); a value outside the f16 range raises `flag`
   // (x3_raise)
@@ -41,7 +45,7 @@ __global__ __launch_bounds__(256) void bert_embed_ln_kernel(const int32_t* __res
   if (row >= M) return;
   int id = ids[row];
   id = id < 0 ? 0 : (id >= BVOCAB ? BVOCAB - 1 : id);
-  const int l = row % L;
+  const int l = posid ? min(max(posid[row], 0), BMAXPOS - 1) : row % L;
   float v[12];
 #pragma unroll
   for (int j = 0; j < 3; ++j) {
@@ -173,14 +177,61 @@ static void launch_ln_rows(const float* x, int M, const float* g, const float* b
 
 // Host launchers (also used by the fp32 path, bert_f32.hip). One wave per token row.
 int launch_bert_embed_ln(const int32_t* ids, int M, int L, const float* emb, float* h32, f16* h16, hipStream_t s,
-                         long long lo, float up) {
+                         long long lo, float up, const int32_t* posid) {
   const float* word = emb;
   const float* pos = word + (size_t)BVOCAB * BH;
   const float* type = pos + (size_t)BMAXPOS * BH;
   const float* lng = type + 2 * BH;
   const float* lnb = lng + BH;
   hipLaunchKernelGGL(bert_embed_ln_kernel, dim3((M + 3) / 4), dim3(256), 0, s, ids, M, L, word, pos, type, lng, lnb,
-                     h32, h16, lo, up, lo ? range_flag() : nullptr);
+                     h32, h16, lo, up, lo ? range_flag() : nullptr, posid);
+  MEC_LAUNCH_CHECK();
+  return 0;
+}
+
+// ----------------------------------------------------------------------------- sentence packing
+// The packed text path (mec_text_fwd_packed): sample i's len[i] tokens sit in slots off[i] .. off[i] +
+// len[i] - 1 of the 128-slot row row[i]. One workgroup per packed row, one thread per slot: the slot's
+// owner is the sample of this row with the largest off <= slot (the plan fills a row from slot 0 with
+// no gaps), its segment id the number of this row's samples that start before the owner. From the
+// padded ids [B, 128] it writes per slot the token id (0 when unused), the position id (the offset
+// inside the sentence; an unused slot's own index) and the uint8 segment id (255 when unused: the
+// unused slots attend only to each other, so their rows stay finite and inside the fp32x3 plane
+// bounds, which hold for any LayerNorm output); and per sample its [CLS] slot row * 128 + off. Every
+// index read from the plan is clamped, so a bad plan gives wrong numbers, not a bad address.
+__global__ __launch_bounds__(128) void bert_pack_kernel(const int32_t* __restrict__ ids,
+                                                        const int32_t* __restrict__ row,
+                                                        const int32_t* __restrict__ off,
+                                                        const int32_t* __restrict__ len, int B, int Bp,
+                                                        int32_t* __restrict__ pids, int32_t* __restrict__ ppos,
+                                                        uint8_t* __restrict__ seg, int32_t* __restrict__ cidx) {
+  const int r = blockIdx.x, t = threadIdx.x;
+  int owner = -1, ooff = -1, before = 0;
+  for (int i = 0; i < B; ++i) {
+    if (row[i] != r) continue;
+    const int o = off[i];
+    if (o > t) continue;
+    ++before;
+    if (o > ooff) { ooff = o; owner = i; }
+  }
+  int id = 0, ps = t, sg = 255;
+  if (owner >= 0 && t - ooff < len[owner] && ooff >= 0) {
+    id = ids[(size_t)owner * ATT_L + (t - ooff)];
+    ps = t - ooff;
+    sg = min(before - 1, 254);
+  }
+  const size_t slot = (size_t)r * ATT_L + t;
+  pids[slot] = id;
+  ppos[slot] = ps;
+  seg[slot] = (uint8_t)sg;
+  for (int i = r * ATT_L + t; i < B; i += Bp * ATT_L)
+    cidx[i] = min(max(row[i], 0), Bp - 1) * ATT_L + min(max(off[i], 0), ATT_L - 1);
+}
+
+int launch_bert_pack(const int32_t* ids, const TextPack& pk, int Bp, int32_t* pids, int32_t* ppos, uint8_t* seg,
+                     int32_t* cidx, hipStream_t s) {
+  hipLaunchKernelGGL(bert_pack_kernel, dim3(Bp), dim3(ATT_L), 0, s, ids, pk.row, pk.off, pk.len, pk.ns, Bp, pids,
+                     ppos, seg, cidx);
   MEC_LAUNCH_CHECK();
   return 0;
 }
@@ -200,8 +251,6 @@ int launch_bert_layernorm(const float* x, int M, const float* g, const float* b,
 // no LDS round trip (k order permuted; V^T is read to match). V stays row-major in LDS
 // (one 16-B write per loaded chunk); its V^T fragments come from ds_read_b64_tr_b16, the
 // gfx950 transposed read (4 keys x 16 d per 16-lane group, delivered column-major).
-constexpr int ATT_L = 128;
-
 __device__ __forceinline__ int aswz(int row, int kc) { return kc ^ ((row >> 1) & 7); }
 // V rows: chunk kc ^ 4 on rows with bit 1 set, so a 32-lane half's four rows x 64 B of a
 // transposed read cover all 64 banks
@@ -216,10 +265,13 @@ __device__ __forceinline__ half4 lds_tr16(const f16* p) {
 // and V (vswz rows) in LDS; sQ's rows are reused to stage the output, which is written to
 // ctx_row0 (query row 0 of this sequence and head, row stride BH).
 // NOUT < 32: only the wave's first NOUT query rows are stored (the [CLS]-only last layer: 1).
-template <int NOUT = 32>
+// PACK: sBias holds the row's segment ids (stage_mask<1>); the query's own slot is 32 wave + lr, or
+// cls_slot for the [CLS]-only form.
+template <int NOUT = 32, int PACK = 0>
 __device__ __forceinline__ void attn_head(f16* sQ, const f16* sK, const f16* sV, const float* sBias, int wave,
-                                          int lane, f16* ctx_row0) {
+                                          int lane, f16* ctx_row0, int cls_slot = 0) {
   const int lr = lane & 31, lh = lane >> 5;
+  const int qseg = mask_qseg<PACK>(sBias, NOUT == 32 ? 32 * wave + lr : cls_slot);
   floatx16 s[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
@@ -241,7 +293,7 @@ __device__ __forceinline__ void attn_head(f16* sQ, const f16* sK, const f16* sV,
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const int key = 32 * t + (e & 3) + 8 * (e >> 2) + 4 * lh;
-      const float v = s[t][e] * 0.125f + sBias[key];  // /sqrt(64) then + additive mask
+      const float v = s[t][e] * 0.125f + mask_term<PACK>(sBias, key, qseg);  // /sqrt(64) then + additive mask
       s[t][e] = v;
       mx = fmaxf(mx, v);
     }
@@ -309,6 +361,7 @@ __device__ __forceinline__ void attn_head(f16* sQ, const f16* sK, const f16* sV,
   }
 }
 
+template <int PACK = 0>  // PACK: mask = the rows' segment ids (stage_mask)
 __global__ __launch_bounds__(256) void bert_attention_kernel(const f16* __restrict__ qkv,
                                                              const int32_t* __restrict__ mask,
                                                              f16* __restrict__ ctx) {
@@ -331,26 +384,32 @@ __global__ __launch_bounds__(256) void bert_attention_kernel(const f16* __restri
     *reinterpret_cast<uint4*>(sK + row * BDH + aswz(row, kc) * 8) = k;
     *reinterpret_cast<uint4*>(sV + row * BDH + vswz(row, kc) * 8) = v;
   }
-  if (tid < ATT_L) sBias[tid] = mask[(size_t)b * ATT_L + tid] ? 0.f : -3.4028234663852886e38f;  // finfo(f32).min
+  stage_mask<PACK>(sBias, mask, b, tid);
   __syncthreads();
-  attn_head(sQ, sK, sV, sBias, wave, lane, ctx + (size_t)b * ATT_L * BH + h * BDH);
+  attn_head<32, PACK>(sQ, sK, sV, sBias, wave, lane, ctx + (size_t)b * ATT_L * BH + h * BDH);
 }
 
 // [CLS]-only attention of BERT's last layer (bert_cls_last): K | V of every token from the K / V
 // GEMM ([B*128, 1536], kv), the [CLS] query row from qc ([B, 768]), the context written compact
 // ([B, 768]). Wave 0 runs attn_head for queries 0..31 with Q rows 1..31 zero (an MFMA output column
 // depends only on its own B column): the [CLS] row has bert_attention_kernel's bits.
+// PACK: workgroup (b, h) serves sample b, whose [CLS] slot is cidx[b] = row * 128 + off: K / V and the
+// segment ids are those of packed row `row`, the query's segment that of slot `off`.
+template <int PACK = 0>
 __global__ __launch_bounds__(256) void bert_attention_cls_kernel(const f16* __restrict__ kv,
                                                                  const int32_t* __restrict__ mask,
                                                                  const f16* __restrict__ qc,
-                                                                 f16* __restrict__ ctx) {
+                                                                 f16* __restrict__ ctx,
+                                                                 const int32_t* __restrict__ cidx) {
   __shared__ __attribute__((aligned(16))) f16 sQ[32 * BDH];
   __shared__ __attribute__((aligned(16))) f16 sK[ATT_L * BDH];
   __shared__ __attribute__((aligned(16))) f16 sV[ATT_L * BDH];
   __shared__ float sBias[ATT_L];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = blockIdx.x / BHEADS, h = blockIdx.x - (blockIdx.x / BHEADS) * BHEADS;
-  const f16* base = kv + (size_t)b * ATT_L * (2 * BH) + h * BDH;
+  const int cs = PACK ? cidx[b] : 0;
+  const int bk = PACK ? cs >> 7 : b;  // the row whose K / V this sample reads
+  const f16* base = kv + (size_t)bk * ATT_L * (2 * BH) + h * BDH;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int c = tid + 256 * i;
@@ -367,9 +426,9 @@ __global__ __launch_bounds__(256) void bert_attention_cls_kernel(const f16* __re
     const uint4 q = row == 0 ? *reinterpret_cast<const uint4*>(qc + (size_t)b * BH + h * BDH + kc * 8) : z;
     *reinterpret_cast<uint4*>(sQ + row * BDH + aswz(row, kc) * 8) = q;
   }
-  if (tid < ATT_L) sBias[tid] = mask[(size_t)b * ATT_L + tid] ? 0.f : -3.4028234663852886e38f;  // finfo(f32).min
+  stage_mask<PACK>(sBias, mask, bk, tid);
   __syncthreads();
-  if (wave == 0) attn_head<1>(sQ, sK, sV, sBias, 0, lane, ctx + (size_t)b * BH + h * BDH);
+  if (wave == 0) attn_head<1, PACK>(sQ, sK, sV, sBias, 0, lane, ctx + (size_t)b * BH + h * BDH, cs & 127);
 }
 
 // ----------------------------------------------------------------------------- fp32x3 attention
@@ -379,11 +438,13 @@ __global__ __launch_bounds__(256) void bert_attention_cls_kernel(const f16* __re
 // softmax, O^T = V^T P^T on split P / V, O -> hi / lo planes staged through this wave's own rows of
 // sK and stored to ctx (row stride BH; lo plane at + clo; CLS: query 0 only). `wave` is the wave's
 // index among the four serving this head; every wave of the workgroup reaches the barrier.
-template <int CLS>
+// PACK: sBias holds the row's segment ids (stage_mask<1>); the query's slot is 32 wave + lr (CLS: cls_slot).
+template <int CLS, int PACK = 0>
 __device__ __forceinline__ void attn_head_x3(f16* const (&sK)[2], const f16* const (&sV)[2], const float* sBias,
                                              const half8 (&qh)[4], const half8 (&ql)[4], int wave, int lane, f16* ctx,
-                                             long long clo, int b, int h, float qks) {
+                                             long long clo, int b, int h, float qks, int cls_slot = 0) {
   const int lr = lane & 31, lh = lane >> 5;
+  const int qseg = mask_qseg<PACK>(sBias, CLS ? cls_slot : 32 * wave + lr);
   floatx16 s[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
@@ -407,7 +468,7 @@ __device__ __forceinline__ void attn_head_x3(f16* const (&sK)[2], const f16* con
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const int key = 32 * t + (e & 3) + 8 * (e >> 2) + 4 * lh;
-      const float v = s[t][e] * qks + sBias[key];  // qks = 1/8 2^-(s_q + s_k) (Q, K planes at 2^s_q, 2^s_k): exact
+      const float v = s[t][e] * qks + mask_term<PACK>(sBias, key, qseg);  // qks = 1/8 2^-(s_q + s_k) (Q, K planes at 2^s_q, 2^s_k): exact
       s[t][e] = v;
       mx = fmaxf(mx, v);
     }
@@ -507,11 +568,15 @@ __device__ __forceinline__ void attn_head_x3(f16* const (&sK)[2], const f16* con
 // stage K and V; wave 0 then runs the full kernel's instruction sequence for queries 0..31 with Q
 // zero for all but query 0 (an MFMA output column depends only on its own B column), so the [CLS]
 // context has the full kernel's bits; waves 1-3 leave after staging.
-template <int CLS = 0>
+// PACK: mask = the rows' segment ids (stage_mask); with CLS, workgroup (b, h) serves sample b, whose [CLS]
+// slot is cidx[b] = row * 128 + off (K / V and segment ids of packed row `row`, the query's segment that of
+// slot `off`).
+template <int CLS = 0, int PACK = 0>
 __global__ __launch_bounds__(256, 2) void bert_attention_x3_kernel(const f16* __restrict__ qkv, long long lo,
                                                                    const int32_t* __restrict__ mask,
                                                                    f16* __restrict__ ctx, long long clo,
-                                                                   const f16* __restrict__ qc, long long qclo, float qks) {
+                                                                   const f16* __restrict__ qc, long long qclo, float qks,
+                                                                   const int32_t* __restrict__ cidx) {
   constexpr int LD = CLS ? 2 * BH : 3 * BH;  // row stride of qkv
   constexpr int KO = CLS ? 0 : BH;           // K column offset (V at KO + BH)
   __shared__ __attribute__((aligned(16))) f16 sK[2][ATT_L * BDH];
@@ -520,6 +585,8 @@ __global__ __launch_bounds__(256, 2) void bert_attention_x3_kernel(const f16* __
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = blockIdx.x / BHEADS, h = blockIdx.x - (blockIdx.x / BHEADS) * BHEADS;
   const int lr = lane & 31, lh = lane >> 5;
+  const int cs = (CLS && PACK) ? cidx[b] : 0;
+  const int bk = (CLS && PACK) ? cs >> 7 : b;  // the row whose K / V are staged
   half8 qh[4], ql[4];  // this lane's Q row 32 wave + lr, k chunks 2 kk + lh (the MFMA B operand)
   if constexpr (CLS) {
     const bool own = wave == 0 && lr == 0;
@@ -543,7 +610,7 @@ __global__ __launch_bounds__(256, 2) void bert_attention_x3_kernel(const f16* __
   }
 #pragma unroll
   for (int pl = 0; pl < 2; ++pl) {
-    const f16* base = qkv + (pl ? lo : 0) + (size_t)b * ATT_L * LD + h * BDH;
+    const f16* base = qkv + (pl ? lo : 0) + (size_t)bk * ATT_L * LD + h * BDH;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int c = tid + 256 * i;
@@ -555,26 +622,34 @@ __global__ __launch_bounds__(256, 2) void bert_attention_x3_kernel(const f16* __
       *reinterpret_cast<uint4*>(sV[pl] + row * BDH + vswz(row, kc) * 8) = v;
     }
   }
-  if (tid < ATT_L) sBias[tid] = mask[(size_t)b * ATT_L + tid] ? 0.f : -3.4028234663852886e38f;  // finfo(f32).min
+  stage_mask<PACK>(sBias, mask, bk, tid);
   __syncthreads();
   if (CLS && wave != 0) return;
   f16* const sKp[2] = {sK[0], sK[1]};
   const f16* const sVp[2] = {sV[0], sV[1]};
-  attn_head_x3<CLS>(sKp, sVp, sBias, qh, ql, wave, lane, ctx, clo, b, h, qks);
+  attn_head_x3<CLS, PACK>(sKp, sVp, sBias, qh, ql, wave, lane, ctx, clo, b, h, qks, cs & 127);
 }
 
 int launch_bert_attention_x3(const f16* qkv, long long lo, const int32_t* mask, f16* ctx, long long clo, int B,
-                             float qks, hipStream_t s) {
-  hipLaunchKernelGGL(bert_attention_x3_kernel<0>, dim3(B * BHEADS), dim3(256), 0, s, qkv, lo, mask, ctx, clo,
-                     nullptr, 0LL, qks);
+                             float qks, hipStream_t s, bool packed) {
+  if (packed)
+    hipLaunchKernelGGL((bert_attention_x3_kernel<0, 1>), dim3(B * BHEADS), dim3(256), 0, s, qkv, lo, mask, ctx, clo,
+                       nullptr, 0LL, qks, nullptr);
+  else
+    hipLaunchKernelGGL((bert_attention_x3_kernel<0, 0>), dim3(B * BHEADS), dim3(256), 0, s, qkv, lo, mask, ctx, clo,
+                       nullptr, 0LL, qks, nullptr);
   MEC_LAUNCH_CHECK();
   return 0;
 }
 
 int launch_bert_attention_x3_cls(const f16* kv, long long lo, const int32_t* mask, const f16* qc, long long qclo,
-                                 f16* ctx, long long clo, int B, float qks, hipStream_t s) {
-  hipLaunchKernelGGL(bert_attention_x3_kernel<1>, dim3(B * BHEADS), dim3(256), 0, s, kv, lo, mask, ctx, clo, qc,
-                     qclo, qks);
+                                 f16* ctx, long long clo, int B, float qks, hipStream_t s, const int32_t* cidx) {
+  if (cidx)
+    hipLaunchKernelGGL((bert_attention_x3_kernel<1, 1>), dim3(B * BHEADS), dim3(256), 0, s, kv, lo, mask, ctx, clo,
+                       qc, qclo, qks, cidx);
+  else
+    hipLaunchKernelGGL((bert_attention_x3_kernel<1, 0>), dim3(B * BHEADS), dim3(256), 0, s, kv, lo, mask, ctx, clo,
+                       qc, qclo, qks, nullptr);
   MEC_LAUNCH_CHECK();
   return 0;
 }
@@ -599,7 +674,8 @@ constexpr int QA_STAGE = (QA_BM + QA_BN) * QA_BK;  // halfs per stage (64 KB)
 // HP = 1 (bert_qkv_attn_heads 1), 4 waves (2 x 2 of the same 64 x 96 wave tile) on a 128 x 192 tile,
 // 40-KB stages and 80 KB of LDS in all (the mask bias inside it), so two workgroups share a CU and one's
 // attention overlaps the other's GEMM. Same sums in the same order: the same bits.
-template <int DBG = 0, int HP = 2>  // probe builds (wrong results): DBG 1 = no attention, 2 = main loop only
+// PACK: mask = the rows' segment ids (stage_mask), nseq the number of packed rows.
+template <int DBG = 0, int HP = 2, int PACK = 0>  // probe builds (wrong results): DBG 1 = no attention, 2 = main loop only
 __global__ __launch_bounds__(256 * HP, HP == 1 ? 2 : 1) void bert_qkv_attn_kernel(const f16* __restrict__ h16,
                                                                                   const f16* __restrict__ wqkv,
                                                                                   const float* __restrict__ bqkv,
@@ -713,7 +789,7 @@ __global__ __launch_bounds__(256 * HP, HP == 1 ? 2 : 1) void bert_qkv_attn_kerne
   }
   // ---- epilogue: (acc + bias) + 0 -> f16 -> the attention's Q / K / V LDS images (every wave is past
   // its last stage read: the loop's second barrier)
-  if (tid < ATT_L) sBias[tid] = mask[(size_t)b * ATT_L + tid] ? 0.f : -3.4028234663852886e38f;  // finfo(f32).min
+  stage_mask<PACK>(sBias, mask, b, tid);
   f16* img = smem;  // [Q (HP heads) | K | V], each [128][64]
 #pragma unroll
   for (int j = 0; j < 6; ++j) {
@@ -742,8 +818,8 @@ __global__ __launch_bounds__(256 * HP, HP == 1 ? 2 : 1) void bert_qkv_attn_kerne
     return;
   }
   const int hh = wave >> 2;
-  attn_head(img + hh * IMG, img + (HP + hh) * IMG, img + (2 * HP + hh) * IMG, sBias, wave & 3, lane,
-            ctx + (size_t)b * ATT_L * BH + (HP * hp + hh) * BDH);
+  attn_head<32, PACK>(img + hh * IMG, img + (HP + hh) * IMG, img + (2 * HP + hh) * IMG, sBias, wave & 3, lane,
+                      ctx + (size_t)b * ATT_L * BH + (HP * hp + hh) * BDH);
 }
 
 // ----------------------------------------------------------------------------- fp32x3 QKV + attention
@@ -770,7 +846,8 @@ __device__ __forceinline__ int qx_sw(int row, int kc) { return kc ^ ((4 - ((row 
 // one workgroup per CU; HP = 1, 4 waves (2 x 2, the same 64 x 96 wave tile) on a 128 x 192 tile, 40-KB
 // stages and 80 KB of LDS in all, so two workgroups share a CU and one's attention phase overlaps the
 // other's GEMM. Both sum every output in the same term and k order: the same bits.
-template <int HP>
+// PACK: mask = the rows' segment ids (stage_mask), nseq the number of packed rows.
+template <int HP, int PACK = 0>
 __global__ __launch_bounds__(256 * HP, HP == 1 ? 2 : 1) void bert_qkv_attn_x3_kernel(
     const f16* __restrict__ hs, long long hlo, const f16* __restrict__ wqkv, long long wlo, float oscale,
     const float* __restrict__ bqkv, const int32_t* __restrict__ mask, f16* __restrict__ ctx, long long clo, int nseq,
@@ -901,7 +978,7 @@ __global__ __launch_bounds__(256 * HP, HP == 1 ? 2 : 1) void bert_qkv_attn_x3_ke
 
   // ---- epilogue: v = (acc 2^-e + b) + 0 (the split GEMM epilogue's expression), hi = f16(v),
   // lo = f16(v - hi). Images: [seg][head][plane] = [128][64] halfs, seg 0 Q / 1 K / 2 V
-  if (tid < ATT_L) sBias[tid] = mask[(size_t)b * ATT_L + tid] ? 0.f : -3.4028234663852886e38f;  // finfo(f32).min
+  stage_mask<PACK>(sBias, mask, b, tid);
   bool bad = false;
   auto write_seg = [&](int want, f16* img) {
 #pragma unroll
@@ -956,17 +1033,24 @@ __global__ __launch_bounds__(256 * HP, HP == 1 ? 2 : 1) void bert_qkv_attn_x3_ke
   __syncthreads();
   f16* const sK[2] = {smem + (0 * HP + hh) * 2 * IMG, smem + ((0 * HP + hh) * 2 + 1) * IMG};
   const f16* const sV[2] = {smem + (1 * HP + hh) * 2 * IMG, smem + ((1 * HP + hh) * 2 + 1) * IMG};
-  attn_head_x3<0>(sK, sV, sBias, qh, ql, aw, lane, ctx, clo, b, HP * hp + hh, qks);
+  attn_head_x3<0, PACK>(sK, sV, sBias, qh, ql, aw, lane, ctx, clo, b, HP * hp + hh, qks);
 }
 
 int launch_bert_qkv_attn_x3(const f16* hs, long long hlo, const f16* wqkv, long long wlo, float oscale,
                             const float* bqkv, const int32_t* mask, f16* ctx, long long clo, int B, float qks,
-                            hipStream_t s) {
-  if (opt().bert_qkv_attn_x3_heads == 1)
-    hipLaunchKernelGGL(bert_qkv_attn_x3_kernel<1>, dim3(B * 12), dim3(256), 0, s, hs, hlo, wqkv, wlo, oscale, bqkv,
+                            hipStream_t s, bool packed) {
+  const int one = opt().bert_qkv_attn_x3_heads == 1;
+  if (one && packed)
+    hipLaunchKernelGGL((bert_qkv_attn_x3_kernel<1, 1>), dim3(B * 12), dim3(256), 0, s, hs, hlo, wqkv, wlo, oscale, bqkv,
+                       mask, ctx, clo, B, qks, range_flag(), opt().qkv_x3_late_dma);
+  else if (packed)
+    hipLaunchKernelGGL((bert_qkv_attn_x3_kernel<2, 1>), dim3(B * 6), dim3(512), 0, s, hs, hlo, wqkv, wlo, oscale, bqkv,
+                       mask, ctx, clo, B, qks, range_flag(), 0);
+  else if (one)
+    hipLaunchKernelGGL((bert_qkv_attn_x3_kernel<1, 0>), dim3(B * 12), dim3(256), 0, s, hs, hlo, wqkv, wlo, oscale, bqkv,
                        mask, ctx, clo, B, qks, range_flag(), opt().qkv_x3_late_dma);
   else
-    hipLaunchKernelGGL(bert_qkv_attn_x3_kernel<2>, dim3(B * 6), dim3(512), 0, s, hs, hlo, wqkv, wlo, oscale, bqkv,
+    hipLaunchKernelGGL((bert_qkv_attn_x3_kernel<2, 0>), dim3(B * 6), dim3(512), 0, s, hs, hlo, wqkv, wlo, oscale, bqkv,
                        mask, ctx, clo, B, qks, range_flag(), 0);
   MEC_LAUNCH_CHECK();
   return 0;
@@ -1147,40 +1231,64 @@ int TextModel::create(const float* blob, size_t n) {
   return 0;
 }
 
+int TextModel::forward_packed(const int32_t* ids, const int32_t* row, const int32_t* off, const int32_t* len, int B,
+                              int Bp, float* cls, float* logits, float* probs, hipStream_t s) {
+  MEC_REQUIRE(B >= 0, "text: B < 0");
+  if (B == 0) return 0;
+  MEC_REQUIRE(ids && row && off && len && cls && logits && probs, "text: null pointer");
+  MEC_REQUIRE(Bp >= 1 && Bp <= B, "text: a packed batch of B samples has 1 <= Bp <= B rows");
+  const TextPack pk{row, off, len, B};
+  return forward(ids, nullptr, Bp, ATT_L, cls, logits, probs, s, &pk);
+}
+
+// pk (or null): the packed form. B is then the number of packed rows, pk->ns the number of samples; the
+// pack kernel builds the slots' ids, position ids and segment ids (which take the mask's place in every
+// attention kernel) and the samples' [CLS] slots, which the [CLS]-row gathers and the [CLS]-only attention
+// read. Every buffer over token rows keeps M = B * 128; every compact [CLS]-row buffer has ns rows.
 int TextModel::forward(const int32_t* ids, const int32_t* mask, int B, int L, float* cls, float* logits,
-                       float* probs, hipStream_t s) {
+                       float* probs, hipStream_t s, const TextPack* pk) {
   MEC_REQUIRE(B >= 0, "text: B < 0");
   if (B == 0) return 0;
   MEC_REQUIRE(L == ATT_L, "text: L must be 128 (padding='max_length', MAX_TEXT_LENGTH=128)");
-  MEC_REQUIRE(ids && mask && cls && logits && probs, "text: null pointer");
-  if (prec == PREC_FP32) return forward_f32(ids, mask, B, L, cls, logits, probs, s);
-  if (prec == PREC_FP32X3) return forward_x3(ids, mask, B, L, cls, logits, probs, s);
+  MEC_REQUIRE(ids && (mask || pk) && cls && logits && probs, "text: null pointer");
+  if (prec == PREC_FP32) return forward_f32(ids, mask, B, L, cls, logits, probs, s, pk);
+  if (prec == PREC_FP32X3) return forward_x3(ids, mask, B, L, cls, logits, probs, s, pk);
   const int M = B * L;
+  const int NS = pk ? pk->ns : B;  // samples: rows of the compact [CLS] buffers and of the outputs
   // workspace: h32 | t32 (f32 [M,768]) ; h16 | ctx16 (f16 [M,768]) ; qkv16 [M,2304] / i16 [M,3072]
   // + the [CLS]-row buffers of the last layer (bert_cls_last): h32c | t32c (f32 [B,768]) ; h16c | qc |
   // ctxc (f16 [B,768]) ; fc (f16 [B,3072]) ; st1c | st2c ([B] float2)
   float *h32, *t32, *pooled, *h32c, *t32c;
   f16 *h16, *ctx16, *big16, *h16c, *qc, *ctxc, *fc;
   float2 *st1, *st1c;
+  PackBufs pkb;
   MEC_TRY(carve(ws, [&](Carver& c) {
     h32 = c.take<float>((size_t)M * BH);
     t32 = c.take<float>((size_t)M * BH);
     h16 = c.take<f16>((size_t)M * BH);
     ctx16 = c.take<f16>((size_t)M * BH);
     big16 = c.take<f16>((size_t)M * BI);  // qkv16 [M,2304] then i16 [M,3072]
-    pooled = c.take<float>((size_t)B * BH);
+    pooled = c.take<float>((size_t)NS * BH);
     st1 = c.take<float2>((size_t)M * 2);  // LN1 | LN2 row stats [M] each
-    h32c = c.take<float>((size_t)B * BH);
-    t32c = c.take<float>((size_t)B * BH);
-    h16c = c.take<f16>((size_t)B * BH);
-    qc = c.take<f16>((size_t)B * BH);
-    ctxc = c.take<f16>((size_t)B * BH);
-    fc = c.take<f16>((size_t)B * BI);
-    st1c = c.take<float2>((size_t)B * 2);
+    h32c = c.take<float>((size_t)NS * BH);
+    t32c = c.take<float>((size_t)NS * BH);
+    h16c = c.take<f16>((size_t)NS * BH);
+    qc = c.take<f16>((size_t)NS * BH);
+    ctxc = c.take<f16>((size_t)NS * BH);
+    fc = c.take<f16>((size_t)NS * BI);
+    st1c = c.take<float2>((size_t)NS * 2);
+    if (pk) pkb.take(c, M, NS);
   }));
   float2* st2 = st1 + M;
-  float2* st2c = st1c + B;
+  float2* st2c = st1c + NS;
   const bool cls_last = opt().bert_cls_last != 0;
+  const int32_t* posid = nullptr;
+  const int32_t* cidx = nullptr;
+  if (pk) {
+    MEC_TRY(launch_bert_pack(ids, *pk, B, pkb.ids, pkb.pos, pkb.seg, pkb.cidx, s));
+    ids = pkb.ids; posid = pkb.pos; cidx = pkb.cidx;
+    mask = reinterpret_cast<const int32_t*>(pkb.seg);
+  }
 
   const float* E = emb.as<float>();
   const float* word = E;
@@ -1190,7 +1298,7 @@ int TextModel::forward(const int32_t* ids, const int32_t* mask, int B, int L, fl
   const float* lnb = lng + BH;
   const dim3 rows_grid((M + 3) / 4);
   hipLaunchKernelGGL(bert_embed_ln_kernel, rows_grid, dim3(256), 0, s, ids, M, L, word, pos, type, lng, lnb, h32,
-                     h16, 0LL, 1.f, nullptr);
+                     h16, 0LL, 1.f, nullptr, posid);
   MEC_LAUNCH_CHECK();
   const f16* W = wts.as<f16>();
   const float* P = prm.as<float>();
@@ -1211,33 +1319,38 @@ int TextModel::forward(const int32_t* ids, const int32_t* mask, int B, int L, fl
       RowGather rg{};
       rg.n = 3;
       rg.src[0] = reinterpret_cast<const char*>(h32); rg.dst[0] = reinterpret_cast<char*>(h32c);
-      rg.sstride[0] = (long long)L * BH * 4; rg.bytes[0] = BH * 4;
+      const long long gs = pk ? 1 : L;  // rows between gathered rows: cidx counts slots
+      rg.idx = cidx;
+      rg.sstride[0] = gs * BH * 4; rg.bytes[0] = BH * 4;
       rg.src[1] = reinterpret_cast<const char*>(h16); rg.dst[1] = reinterpret_cast<char*>(h16c);
-      rg.sstride[1] = (long long)L * BH * 2; rg.bytes[1] = BH * 2;
+      rg.sstride[1] = gs * BH * 2; rg.bytes[1] = BH * 2;
       rg.src[2] = reinterpret_cast<const char*>(st2); rg.dst[2] = reinterpret_cast<char*>(st2c);
-      rg.sstride[2] = (long long)L * 8; rg.bytes[2] = 8;
-      MEC_TRY(launch_gather_rows(rg, B, s));
+      rg.sstride[2] = gs * 8; rg.bytes[2] = 8;
+      MEC_TRY(launch_gather_rows(rg, NS, s));
       g.A = h16; g.B = wqkv + (size_t)BH * BH; g.bias = bqkv + BH; g.C16 = big16; g.M = M; g.N = 2 * BH; g.K = BH;
       MEC_TRY(launch_gemm(g, s, &prof, TAG_NONE));  // K | V [M, 1536]
       g = GemmParams();
-      g.A = h16c; g.B = wqkv; g.bias = bqkv; g.C16 = qc; g.M = B; g.N = BH; g.K = BH;
+      g.A = h16c; g.B = wqkv; g.bias = bqkv; g.C16 = qc; g.M = NS; g.N = BH; g.K = BH;
       MEC_TRY(launch_gemm(g, s, &prof, TAG_NONE));  // Q of the [CLS] rows
-      hipLaunchKernelGGL(bert_attention_cls_kernel, dim3(B * BHEADS), dim3(256), 0, s, big16, mask, qc, ctxc);
+      if (pk)
+        hipLaunchKernelGGL(bert_attention_cls_kernel<1>, dim3(NS * BHEADS), dim3(256), 0, s, big16, mask, qc, ctxc, cidx);
+      else
+        hipLaunchKernelGGL(bert_attention_cls_kernel<0>, dim3(B * BHEADS), dim3(256), 0, s, big16, mask, qc, ctxc, nullptr);
       MEC_LAUNCH_CHECK();
       g = GemmParams();
       g.A = ctxc; g.B = wo; g.bias = bo; g.R = h32c; g.r_f32 = 1; g.r_stats = st2c; g.r_g = pg2; g.r_b = pg2 + BH;
-      g.C32 = t32c; g.M = B; g.N = BH; g.K = BH;
+      g.C32 = t32c; g.M = NS; g.N = BH; g.K = BH;
       MEC_TRY(launch_gemm(g, s, &prof, TAG_NONE));
-      launch_ln_rows(t32c, B, g1, b1, nullptr, h16c, st1c, s, 0, 1.f);
+      launch_ln_rows(t32c, NS, g1, b1, nullptr, h16c, st1c, s, 0, 1.f);
       MEC_LAUNCH_CHECK();
       g = GemmParams();
-      g.A = h16c; g.B = wi; g.bias = bi; g.act = ACT_GELU; g.C16 = fc; g.M = B; g.N = BI; g.K = BH;
+      g.A = h16c; g.B = wi; g.bias = bi; g.act = ACT_GELU; g.C16 = fc; g.M = NS; g.N = BI; g.K = BH;
       MEC_TRY(launch_gemm(g, s, &prof, TAG_NONE));
       g = GemmParams();
       g.A = fc; g.B = wo2; g.bias = bo2; g.R = t32c; g.r_f32 = 1; g.r_stats = st1c; g.r_g = g1; g.r_b = b1;
-      g.C32 = h32c; g.M = B; g.N = BH; g.K = BI;
+      g.C32 = h32c; g.M = NS; g.N = BH; g.K = BI;
       MEC_TRY(launch_gemm(g, s, &prof, TAG_NONE));
-      launch_ln_rows(h32c, B, g2, b2, h32c, h16c, st2c, s, 0, 1.f);  // in place, written in full (the pooler's input)
+      launch_ln_rows(h32c, NS, g2, b2, h32c, h16c, st2c, s, 0, 1.f);  // in place, written in full (the pooler's input)
       MEC_LAUNCH_CHECK();
       break;
     }
@@ -1250,7 +1363,11 @@ int TextModel::forward(const int32_t* ids, const int32_t* mask, int B, int L, fl
         hipLaunchKernelGGL((bert_qkv_attn_kernel<2>), dim3(B * 6), dim3(512), 0, s, h16, wqkv, bqkv, mask, ctx16, B);
       else
 #endif
-      if (opt().bert_qkv_attn_heads == 1)
+      if (opt().bert_qkv_attn_heads == 1 && pk)
+        hipLaunchKernelGGL((bert_qkv_attn_kernel<0, 1, 1>), dim3(B * 12), dim3(256), 0, s, h16, wqkv, bqkv, mask, ctx16, B);
+      else if (pk)
+        hipLaunchKernelGGL((bert_qkv_attn_kernel<0, 2, 1>), dim3(B * 6), dim3(512), 0, s, h16, wqkv, bqkv, mask, ctx16, B);
+      else if (opt().bert_qkv_attn_heads == 1)
         hipLaunchKernelGGL((bert_qkv_attn_kernel<0, 1>), dim3(B * 12), dim3(256), 0, s, h16, wqkv, bqkv, mask, ctx16, B);
       else
         hipLaunchKernelGGL((bert_qkv_attn_kernel<0>), dim3(B * 6), dim3(512), 0, s, h16, wqkv, bqkv, mask, ctx16, B);
@@ -1260,7 +1377,10 @@ int TextModel::forward(const int32_t* ids, const int32_t* mask, int B, int L, fl
       g.A = h16; g.B = wqkv; g.bias = bqkv; g.C16 = big16; g.M = M; g.N = 2304; g.K = BH;
       MEC_TRY(launch_gemm(g, s, &prof, TAG_BERT_QKV));
       MEC_TRY(prof.begin(TAG_BERT_ATTN, s));
-      hipLaunchKernelGGL(bert_attention_kernel, dim3(B * BHEADS), dim3(256), 0, s, big16, mask, ctx16);
+      if (pk)
+        hipLaunchKernelGGL(bert_attention_kernel<1>, dim3(B * BHEADS), dim3(256), 0, s, big16, mask, ctx16);
+      else
+        hipLaunchKernelGGL(bert_attention_kernel<0>, dim3(B * BHEADS), dim3(256), 0, s, big16, mask, ctx16);
       MEC_LAUNCH_CHECK();
       MEC_TRY(prof.end(TAG_BERT_ATTN, s));
     }
@@ -1296,10 +1416,18 @@ int TextModel::forward(const int32_t* ids, const int32_t* mask, int B, int L, fl
   const float* head = P + PRM_LAYER * BLAYERS;
   const float *WpT = head, *bp = WpT + (size_t)BH * BH, *WcT = bp + BH, *bc = WcT + (size_t)BH * 7;
   // pooler: tanh(cls . Wp^T + bp) over the batch (also copies the CLS feature out)
-  const bool compact = cls_last && BLAYERS > 1;
-  MEC_TRY(launch_linear_mfma<BACT_TANH>(compact ? h32c : h32, compact ? (size_t)BH : (size_t)L * BH, B, BH, WpT, bp,
+  bool compact = cls_last && BLAYERS > 1;
+  if (pk && !compact) {  // the samples' [CLS] rows of the final h32, in sample order
+    RowGather rg{};
+    rg.n = 1; rg.idx = cidx;
+    rg.src[0] = reinterpret_cast<const char*>(h32); rg.dst[0] = reinterpret_cast<char*>(h32c);
+    rg.sstride[0] = BH * 4; rg.bytes[0] = BH * 4;
+    MEC_TRY(launch_gather_rows(rg, NS, s));
+    compact = true;
+  }
+  MEC_TRY(launch_linear_mfma<BACT_TANH>(compact ? h32c : h32, compact ? (size_t)BH : (size_t)L * BH, NS, BH, WpT, bp,
                                         BH, pooled, BH, cls, BH, s));
-  MEC_TRY(launch_head7(pooled, B, BH, WcT, bc, logits, probs, s));
+  MEC_TRY(launch_head7(pooled, NS, BH, WcT, bc, logits, probs, s));
   return 0;
 }
 

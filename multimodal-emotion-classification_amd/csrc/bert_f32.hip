@@ -38,18 +38,24 @@ __device__ __forceinline__ int kswz(int row, int c) { return c ^ (row & 15); }
 // row comes from qc ([B, 768]) and the context is written compact ([B, 768]); wave 0 computes
 // queries 0..31 with Q zero for all but query 0 (an MFMA output column depends only on its own B
 // column: the [CLS] context has the full kernel's bits), waves 1-3 only stage K and V.
-template <int SPLIT = 0, int CLS = 0>
+// PACK (the packed text path): mask = the rows' uint8 segment ids (block_ops.h stage_mask) and a key
+// counts only in the query's own segment; with CLS, workgroup (b, h) serves sample b, whose [CLS] slot is
+// cidx[b] = row * 128 + off (K / V and segment ids of packed row `row`, the query's segment that of `off`).
+template <int SPLIT = 0, int CLS = 0, int PACK = 0>
 __global__ __launch_bounds__(256, 2) void bert_attention_f32_kernel(const float* __restrict__ qkv,
                                                                     const int32_t* __restrict__ mask,
                                                                     float* __restrict__ ctx, f16* __restrict__ ctx16,
-                                                                    long long lo, const float* __restrict__ qc) {
+                                                                    long long lo, const float* __restrict__ qc,
+                                                                    const int32_t* __restrict__ cidx) {
   constexpr int LD = CLS ? 2 * H : 3 * H, KO = CLS ? 0 : H;
   __shared__ __attribute__((aligned(16))) float sK[AL * DH];
   __shared__ __attribute__((aligned(16))) float sV[AL * DH];
   __shared__ float sBias[AL];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = blockIdx.x / NH, h = blockIdx.x - (blockIdx.x / NH) * NH;
-  const float* base = qkv + (size_t)b * AL * LD + h * DH;
+  const int cs = (CLS && PACK) ? cidx[b] : 0;
+  const int bk = (CLS && PACK) ? cs >> 7 : b;  // the row whose K / V are staged
+  const float* base = qkv + (size_t)bk * AL * LD + h * DH;
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     const int c = tid + 256 * i;
@@ -60,7 +66,7 @@ __global__ __launch_bounds__(256, 2) void bert_attention_f32_kernel(const float*
     *reinterpret_cast<float4*>(sK + row * DH + kswz(row, kc) * 4) = k;
     *reinterpret_cast<float4*>(sV + row * DH + kc * 4) = v;
   }
-  if (tid < AL) sBias[tid] = mask[(size_t)b * AL + tid] ? 0.f : -3.4028234663852886e38f;  // finfo(f32).min
+  stage_mask<PACK>(sBias, mask, bk, tid);
   const int lr = lane & 31, lh = lane >> 5;
   const int q = 32 * wave + lr;
   float4 qf[8];  // Q[q][8s + 4lh .. +3]
@@ -76,6 +82,7 @@ __global__ __launch_bounds__(256, 2) void bert_attention_f32_kernel(const float*
   }
   __syncthreads();
   if (CLS && wave != 0) return;
+  const int qseg = mask_qseg<PACK>(sBias, CLS ? (cs & 127) : q);
 
   floatx16 st[4];  // st[t][e] = S[q][key 32t + (e&3) + 8(e>>2) + 4lh]
 #pragma unroll
@@ -99,7 +106,7 @@ __global__ __launch_bounds__(256, 2) void bert_attention_f32_kernel(const float*
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const int key = 32 * t + (e & 3) + 8 * (e >> 2) + 4 * lh;
-      const float v = st[t][e] * 0.125f + sBias[key];
+      const float v = st[t][e] * 0.125f + mask_term<PACK>(sBias, key, qseg);
       st[t][e] = v;
       mx = fmaxf(mx, v);
     }
@@ -154,27 +161,38 @@ __global__ __launch_bounds__(256, 2) void bert_attention_f32_kernel(const float*
 }
 
 int TextModel::forward_f32(const int32_t* ids, const int32_t* mask, int B, int L, float* cls, float* logits,
-                           float* probs, hipStream_t s) {
+                           float* probs, hipStream_t s, const TextPack* pk) {
   MEC_REQUIRE(wts32.p, "text: fp32 weights missing (handle created at f16 precision)");
   const int M = B * L;
+  const int NS = pk ? pk->ns : B;  // samples (TextModel::forward): rows of the compact buffers and the outputs
   // workspace: h32 | t32 | ctx32 (f32 [M,768]) ; big32 f32 [M,3072] (qkv [M,2304], then FFN) ; pooled [B,768] ;
   // the [CLS]-row buffers of the last layer (bert_cls_last): h32c | t32c | qc | ctxc [B,768], fc [B,3072]
   float *h32, *t32, *ctx32, *big32, *pooled, *h32c, *t32c, *qc, *ctxc, *fc;
+  PackBufs pkb;
   MEC_TRY(carve(ws, [&](Carver& c) {
     h32 = c.take<float>((size_t)M * H);
     t32 = c.take<float>((size_t)M * H);
     ctx32 = c.take<float>((size_t)M * H);
     big32 = c.take<float>((size_t)M * FF);
-    pooled = c.take<float>((size_t)B * H);
-    h32c = c.take<float>((size_t)B * H);
-    t32c = c.take<float>((size_t)B * H);
-    qc = c.take<float>((size_t)B * H);
-    ctxc = c.take<float>((size_t)B * H);
-    fc = c.take<float>((size_t)B * FF);
+    pooled = c.take<float>((size_t)NS * H);
+    h32c = c.take<float>((size_t)NS * H);
+    t32c = c.take<float>((size_t)NS * H);
+    qc = c.take<float>((size_t)NS * H);
+    ctxc = c.take<float>((size_t)NS * H);
+    fc = c.take<float>((size_t)NS * FF);
+    if (pk) pkb.take(c, M, NS);
   }));
   const bool cls_last = opt().bert_cls_last != 0;
+  const int32_t* posid = nullptr;
+  const int32_t* cidx = nullptr;
+  if (pk) {
+    MEC_TRY(launch_bert_pack(ids, *pk, B, pkb.ids, pkb.pos, pkb.seg, pkb.cidx, s));
+    ids = pkb.ids; posid = pkb.pos; cidx = pkb.cidx;
+    mask = reinterpret_cast<const int32_t*>(pkb.seg);
+  }
+  const long long gs = pk ? 1 : AL;  // rows between gathered [CLS] rows: cidx counts slots
 
-  MEC_TRY(launch_bert_embed_ln(ids, M, L, emb.as<float>(), h32, nullptr, s));
+  MEC_TRY(launch_bert_embed_ln(ids, M, L, emb.as<float>(), h32, nullptr, s, 0, 1.f, posid));
   const float* W = wts32.as<float>();
   const float* P = prm.as<float>();
   for (int l = 0; l < NL; ++l) {
@@ -189,36 +207,44 @@ int TextModel::forward_f32(const int32_t* ids, const int32_t* mask, int B, int L
     if (cls_last && l == NL - 1) {
       // [CLS]-only last layer (TextModel::forward): K / V for every token, the rest on the [CLS] rows
       RowGather rg{};
-      rg.n = 1;
+      rg.n = 1; rg.idx = cidx;
       rg.src[0] = reinterpret_cast<const char*>(h32); rg.dst[0] = reinterpret_cast<char*>(h32c);
-      rg.sstride[0] = (long long)AL * H * 4; rg.bytes[0] = H * 4;
-      MEC_TRY(launch_gather_rows(rg, B, s));
+      rg.sstride[0] = gs * H * 4; rg.bytes[0] = H * 4;
+      MEC_TRY(launch_gather_rows(rg, NS, s));
       g.A = h32; g.B32 = wqkv + (size_t)H * H; g.bias = bqkv + H; g.C32 = big32; g.M = M; g.N = 2 * H; g.K = H;
       MEC_TRY(launch_gemm_f32(g, s, &prof, TAG_NONE));  // K | V [M, 1536]
       g = GemmParams();
-      g.A = h32c; g.B32 = wqkv; g.bias = bqkv; g.C32 = qc; g.M = B; g.N = H; g.K = H;
+      g.A = h32c; g.B32 = wqkv; g.bias = bqkv; g.C32 = qc; g.M = NS; g.N = H; g.K = H;
       MEC_TRY(launch_gemm_f32(g, s, &prof, TAG_NONE));  // Q of the [CLS] rows
-      hipLaunchKernelGGL((bert_attention_f32_kernel<0, 1>), dim3(B * NH), dim3(256), 0, s, big32, mask, ctxc, nullptr,
-                         0LL, qc);
+      if (pk)
+        hipLaunchKernelGGL((bert_attention_f32_kernel<0, 1, 1>), dim3(NS * NH), dim3(256), 0, s, big32, mask, ctxc,
+                           nullptr, 0LL, qc, cidx);
+      else
+        hipLaunchKernelGGL((bert_attention_f32_kernel<0, 1, 0>), dim3(B * NH), dim3(256), 0, s, big32, mask, ctxc,
+                           nullptr, 0LL, qc, nullptr);
       MEC_LAUNCH_CHECK();
       g = GemmParams();
-      g.A = ctxc; g.B32 = wo; g.bias = bo; g.R = h32c; g.r_f32 = 1; g.C32 = t32c; g.M = B; g.N = H; g.K = H;
+      g.A = ctxc; g.B32 = wo; g.bias = bo; g.R = h32c; g.r_f32 = 1; g.C32 = t32c; g.M = NS; g.N = H; g.K = H;
       MEC_TRY(launch_gemm_f32(g, s, &prof, TAG_NONE));
-      MEC_TRY(launch_bert_layernorm(t32c, B, g1, b1, h32c, nullptr, nullptr, s));
+      MEC_TRY(launch_bert_layernorm(t32c, NS, g1, b1, h32c, nullptr, nullptr, s));
       g = GemmParams();
-      g.A = h32c; g.B32 = wi; g.bias = bi; g.act = ACT_GELU_EXACT; g.C32 = fc; g.M = B; g.N = FF; g.K = H;
+      g.A = h32c; g.B32 = wi; g.bias = bi; g.act = ACT_GELU_EXACT; g.C32 = fc; g.M = NS; g.N = FF; g.K = H;
       MEC_TRY(launch_gemm_f32(g, s, &prof, TAG_NONE));
       g = GemmParams();
-      g.A = fc; g.B32 = wo2; g.bias = bo2; g.R = h32c; g.r_f32 = 1; g.C32 = t32c; g.M = B; g.N = H; g.K = FF;
+      g.A = fc; g.B32 = wo2; g.bias = bo2; g.R = h32c; g.r_f32 = 1; g.C32 = t32c; g.M = NS; g.N = H; g.K = FF;
       MEC_TRY(launch_gemm_f32(g, s, &prof, TAG_NONE));
-      MEC_TRY(launch_bert_layernorm(t32c, B, g2, b2, h32c, nullptr, nullptr, s));
+      MEC_TRY(launch_bert_layernorm(t32c, NS, g2, b2, h32c, nullptr, nullptr, s));
       break;
     }
     g.A = h32; g.B32 = wqkv; g.bias = bqkv; g.C32 = big32; g.M = M; g.N = 2304; g.K = H;
     MEC_TRY(launch_gemm_f32(g, s, &prof, TAG_BERT_QKV));
     MEC_TRY(prof.begin(TAG_BERT_ATTN, s));
-    hipLaunchKernelGGL((bert_attention_f32_kernel<0, 0>), dim3(B * NH), dim3(256), 0, s, big32, mask, ctx32, nullptr, 0LL,
-                       nullptr);
+    if (pk)
+      hipLaunchKernelGGL((bert_attention_f32_kernel<0, 0, 1>), dim3(B * NH), dim3(256), 0, s, big32, mask, ctx32, nullptr,
+                         0LL, nullptr, nullptr);
+    else
+      hipLaunchKernelGGL((bert_attention_f32_kernel<0, 0, 0>), dim3(B * NH), dim3(256), 0, s, big32, mask, ctx32, nullptr,
+                         0LL, nullptr, nullptr);
     MEC_LAUNCH_CHECK();
     MEC_TRY(prof.end(TAG_BERT_ATTN, s));
     g = GemmParams();
@@ -239,9 +265,18 @@ int TextModel::forward_f32(const int32_t* ids, const int32_t* mask, int B, int L
   }
   const float* head = P + PRM_LAYER * NL;
   const float *WpT = head, *bp = WpT + (size_t)H * H, *WcT = bp + H, *bc = WcT + (size_t)H * 7;
-  MEC_TRY(launch_linear_mfma<BACT_TANH>(cls_last ? h32c : h32, cls_last ? (size_t)H : (size_t)L * H, B, H, WpT, bp,
+  bool compact = cls_last;
+  if (pk && !compact) {  // the samples' [CLS] rows of the final h32, in sample order
+    RowGather rg{};
+    rg.n = 1; rg.idx = cidx;
+    rg.src[0] = reinterpret_cast<const char*>(h32); rg.dst[0] = reinterpret_cast<char*>(h32c);
+    rg.sstride[0] = H * 4; rg.bytes[0] = H * 4;
+    MEC_TRY(launch_gather_rows(rg, NS, s));
+    compact = true;
+  }
+  MEC_TRY(launch_linear_mfma<BACT_TANH>(compact ? h32c : h32, compact ? (size_t)H : (size_t)L * H, NS, H, WpT, bp,
                                         H, pooled, H, cls, H, s));
-  MEC_TRY(launch_head7(pooled, B, H, WcT, bc, logits, probs, s));
+  MEC_TRY(launch_head7(pooled, NS, H, WcT, bc, logits, probs, s));
   return 0;
 }
 
@@ -256,26 +291,28 @@ int TextModel::forward_f32(const int32_t* ids, const int32_t* mask, int B, int L
 //   h32         = i . Wo2^T 2^-e + bo2 + LN1'(t32)                  split GEMM (deferred LN)
 //   h hi/lo, st2 = LN(h32)
 int TextModel::forward_x3(const int32_t* ids, const int32_t* mask, int B, int L, float* cls, float* logits,
-                          float* probs, hipStream_t s) {
+                          float* probs, hipStream_t s, const TextPack* pk) {
   MEC_REQUIRE(wts.p && x3_lo && x3_scale.size() == 4 * NL, "text: fp32x3 weights missing");
   const int M = B * L;
+  const int NS = pk ? pk->ns : B;  // samples (TextModel::forward): rows of the compact buffers and the outputs
   const long long MH = (long long)M * H, MF = (long long)M * FF;
   // workspace: h32 | t32 (f32 [M,768]) ; h hi|lo, ctx hi|lo (f16 2x[M,768]) ; big: qkv hi|lo
   // (f16 2x[M,2304]), then the FFN intermediate hi|lo (f16 2x[M,3072]) ; pooled [B,768]
   // + the [CLS]-row buffers of the last layer (bert_cls_last): h32c | t32c (f32 [B,768]) ; hsc | qsc | csc
   // (f16 planes 2x[B,768]) ; fsc (f16 planes 2x[B,3072])
-  const long long BHc = (long long)B * H, BFc = (long long)B * FF;
+  const long long BHc = (long long)NS * H, BFc = (long long)NS * FF;
   // + the LayerNorm row stats st1 | st2 ([M] float2; deferred LayerNorm, below) and st2c ([B] float2)
   float *h32, *t32, *pooled, *h32c, *t32c;
   f16 *hs, *cs, *bigs, *hsc, *qsc, *csc, *fsc;
   float2 *st1, *st2c;
+  PackBufs pkb;
   MEC_TRY(carve(ws, [&](Carver& c) {
     h32 = c.take<float>((size_t)MH);
     t32 = c.take<float>((size_t)MH);
     hs = c.take<f16>((size_t)MH * 2);
     cs = c.take<f16>((size_t)MH * 2);
     bigs = c.take<f16>((size_t)MF * 2);
-    pooled = c.take<float>((size_t)B * H);
+    pooled = c.take<float>((size_t)NS * H);
     h32c = c.take<float>((size_t)BHc);
     t32c = c.take<float>((size_t)BHc);
     hsc = c.take<f16>((size_t)BHc * 2);
@@ -283,13 +320,22 @@ int TextModel::forward_x3(const int32_t* ids, const int32_t* mask, int B, int L,
     csc = c.take<f16>((size_t)BHc * 2);
     fsc = c.take<f16>((size_t)BFc * 2);
     st1 = c.take<float2>((size_t)M * 2);  // LN1 | LN2 row stats [M] each
-    st2c = c.take<float2>((size_t)B);     // LN2 row stats of the [CLS] rows
+    st2c = c.take<float2>((size_t)NS);    // LN2 row stats of the [CLS] rows
+    if (pk) pkb.take(c, M, NS);
   }));
   float2* st2 = st1 + M;
   const bool cls_last = opt().bert_cls_last != 0;
   const int gelu_act = opt().gelu_x3 ? ACT_GELU_F32 : ACT_GELU_EXACT;  // FFN1's erf GELU
+  const int32_t* posid = nullptr;
+  const int32_t* cidx = nullptr;
+  if (pk) {
+    MEC_TRY(launch_bert_pack(ids, *pk, B, pkb.ids, pkb.pos, pkb.seg, pkb.cidx, s));
+    ids = pkb.ids; posid = pkb.pos; cidx = pkb.cidx;
+    mask = reinterpret_cast<const int32_t*>(pkb.seg);
+  }
+  const long long gs = pk ? 1 : AL;  // rows between gathered [CLS] rows: cidx counts slots
 
-  MEC_TRY(launch_bert_embed_ln(ids, M, L, emb.as<float>(), h32, hs, s, MH, std::ldexp(1.0f, x3_s_emb)));
+  MEC_TRY(launch_bert_embed_ln(ids, M, L, emb.as<float>(), h32, hs, s, MH, std::ldexp(1.0f, x3_s_emb), posid));
   const f16* W = wts.as<f16>();
   const float* P = prm.as<float>();
   const long long wlo = (long long)x3_lo;
@@ -313,19 +359,19 @@ int TextModel::forward_x3(const int32_t* ids, const int32_t* mask, int B, int L,
     if (cls_last && l == NL - 1) {
       // [CLS]-only last layer (TextModel::forward): K / V for every token, the rest on the [CLS] rows
       RowGather rg{};
-      rg.n = 3;
+      rg.n = 3; rg.idx = cidx;
       rg.src[0] = reinterpret_cast<const char*>(h32); rg.dst[0] = reinterpret_cast<char*>(h32c);
-      rg.sstride[0] = (long long)AL * H * 4; rg.bytes[0] = H * 4;
+      rg.sstride[0] = gs * H * 4; rg.bytes[0] = H * 4;
       rg.src[1] = reinterpret_cast<const char*>(hs); rg.dst[1] = reinterpret_cast<char*>(hsc);
-      rg.sstride[1] = (long long)AL * H * 2; rg.bytes[1] = H * 2;
+      rg.sstride[1] = gs * H * 2; rg.bytes[1] = H * 2;
       rg.src[2] = reinterpret_cast<const char*>(hs + MH); rg.dst[2] = reinterpret_cast<char*>(hsc + BHc);
-      rg.sstride[2] = (long long)AL * H * 2; rg.bytes[2] = H * 2;
+      rg.sstride[2] = gs * H * 2; rg.bytes[2] = H * 2;
       if (l > 0) {  // h32 holds layer l-1's pre-LN2 sum (deferred LayerNorm): its stats too
         rg.n = 4;
         rg.src[3] = reinterpret_cast<const char*>(st2); rg.dst[3] = reinterpret_cast<char*>(st2c);
-        rg.sstride[3] = (long long)AL * 8; rg.bytes[3] = 8;
+        rg.sstride[3] = gs * 8; rg.bytes[3] = 8;
       }
-      MEC_TRY(launch_gather_rows(rg, B, s));
+      MEC_TRY(launch_gather_rows(rg, NS, s));
       const float* pg2 = P + PRM_LAYER * (l - 1) + 8448;  // layer l-1's LN2 (g2, b2)
       const long long kvlo = (long long)M * 2 * H;
       g.split = 1; g.A = hs; g.a_lo = MH; g.B = wqkv + (size_t)H * H; g.b_lo = wlo; g.oscale = sc[0];
@@ -333,24 +379,24 @@ int TextModel::forward_x3(const int32_t* ids, const int32_t* mask, int B, int L,
       MEC_TRY(launch_gemm(g, s, &prof, TAG_NONE));  // K | V planes [M, 1536]
       g = GemmParams();
       g.split = 1; g.A = hsc; g.a_lo = BHc; g.B = wqkv; g.b_lo = wlo; g.oscale = sc[0];
-      g.bias = bqkv; g.C16 = qsc; g.c_lo = BHc; g.M = B; g.N = H; g.K = H;
+      g.bias = bqkv; g.C16 = qsc; g.c_lo = BHc; g.M = NS; g.N = H; g.K = H;
       MEC_TRY(launch_gemm(g, s, &prof, TAG_NONE));  // Q planes of the [CLS] rows
-      MEC_TRY(launch_bert_attention_x3_cls(bigs, kvlo, mask, qsc, BHc, csc, BHc, B, qks, s));
+      MEC_TRY(launch_bert_attention_x3_cls(bigs, kvlo, mask, qsc, BHc, csc, BHc, NS, qks, s, cidx));
       g = GemmParams();
       g.split = 1; g.A = csc; g.a_lo = BHc; g.B = wo; g.b_lo = wlo; g.oscale = sc[1];
-      g.bias = bo; g.R = h32c; g.r_f32 = 1; g.C32 = t32c; g.M = B; g.N = H; g.K = H;
+      g.bias = bo; g.R = h32c; g.r_f32 = 1; g.C32 = t32c; g.M = NS; g.N = H; g.K = H;
       if (l > 0) { g.r_stats = st2c; g.r_g = pg2; g.r_b = pg2 + H; }
       MEC_TRY(launch_gemm(g, s, &prof, TAG_NONE));
-      MEC_TRY(launch_bert_layernorm(t32c, B, g1, b1, h32c, hsc, nullptr, s, BHc, up1));
+      MEC_TRY(launch_bert_layernorm(t32c, NS, g1, b1, h32c, hsc, nullptr, s, BHc, up1));
       g = GemmParams();
       g.split = 1; g.A = hsc; g.a_lo = BHc; g.B = wi; g.b_lo = wlo; g.oscale = sc[2];
-      g.bias = bi; g.act = gelu_act; g.C16 = fsc; g.c_lo = BFc; g.cscale = ffs; g.M = B; g.N = FF; g.K = H;
+      g.bias = bi; g.act = gelu_act; g.C16 = fsc; g.c_lo = BFc; g.cscale = ffs; g.M = NS; g.N = FF; g.K = H;
       MEC_TRY(launch_gemm(g, s, &prof, TAG_NONE));
       g = GemmParams();
       g.split = 1; g.A = fsc; g.a_lo = BFc; g.B = wo2; g.b_lo = wlo; g.oscale = sc[3];
-      g.bias = bo2; g.R = h32c; g.r_f32 = 1; g.C32 = t32c; g.M = B; g.N = H; g.K = FF;
+      g.bias = bo2; g.R = h32c; g.r_f32 = 1; g.C32 = t32c; g.M = NS; g.N = H; g.K = FF;
       MEC_TRY(launch_gemm(g, s, &prof, TAG_NONE));
-      MEC_TRY(launch_bert_layernorm(t32c, B, g2, b2, h32c, hsc, nullptr, s, BHc, up2));
+      MEC_TRY(launch_bert_layernorm(t32c, NS, g2, b2, h32c, hsc, nullptr, s, BHc, up2));
       break;
     }
     // QKV projection + attention fused (Q / K / V stay on chip). The fused kernel sums in the K-interleaved
@@ -358,14 +404,14 @@ int TextModel::forward_x3(const int32_t* ids, const int32_t* mask, int B, int L,
     // and every split product of the forward keeps one term order
     if (opt().bert_qkv_attn == 1 && L == 128 && opt().gemm_x3_order == 1) {
       MEC_TRY(prof.begin(TAG_BERT_QKV, s));
-      MEC_TRY(launch_bert_qkv_attn_x3(hs, MH, wqkv, wlo, sc[0], bqkv, mask, cs, MH, B, qks, s));
+      MEC_TRY(launch_bert_qkv_attn_x3(hs, MH, wqkv, wlo, sc[0], bqkv, mask, cs, MH, B, qks, s, pk != nullptr));
       MEC_TRY(prof.end(TAG_BERT_QKV, s));
     } else {
       g.split = 1; g.A = hs; g.a_lo = MH; g.B = wqkv; g.b_lo = wlo; g.oscale = sc[0];
       g.bias = bqkv; g.C16 = bigs; g.c_lo = (long long)M * 2304; g.M = M; g.N = 2304; g.K = H;
       MEC_TRY(launch_gemm(g, s, &prof, TAG_BERT_QKV));
       MEC_TRY(prof.begin(TAG_BERT_ATTN, s));
-      MEC_TRY(launch_bert_attention_x3(bigs, (long long)M * 2304, mask, cs, MH, B, qks, s));
+      MEC_TRY(launch_bert_attention_x3(bigs, (long long)M * 2304, mask, cs, MH, B, qks, s, pk != nullptr));
       MEC_TRY(prof.end(TAG_BERT_ATTN, s));
     }
     // deferred LayerNorm (as on the f16 path): the LN kernels write the GEMM operand planes and the
@@ -399,9 +445,18 @@ int TextModel::forward_x3(const int32_t* ids, const int32_t* mask, int B, int L,
   }
   const float* head = P + PRM_LAYER * NL;
   const float *WpT = head, *bp = WpT + (size_t)H * H, *WcT = bp + H, *bc = WcT + (size_t)H * 7;
-  MEC_TRY(launch_linear_mfma<BACT_TANH>(cls_last ? h32c : h32, cls_last ? (size_t)H : (size_t)L * H, B, H, WpT, bp,
+  bool compact = cls_last;
+  if (pk && !compact) {  // the samples' [CLS] rows of the final h32, in sample order
+    RowGather rg{};
+    rg.n = 1; rg.idx = cidx;
+    rg.src[0] = reinterpret_cast<const char*>(h32); rg.dst[0] = reinterpret_cast<char*>(h32c);
+    rg.sstride[0] = H * 4; rg.bytes[0] = H * 4;
+    MEC_TRY(launch_gather_rows(rg, NS, s));
+    compact = true;
+  }
+  MEC_TRY(launch_linear_mfma<BACT_TANH>(compact ? h32c : h32, compact ? (size_t)H : (size_t)L * H, NS, H, WpT, bp,
                                         H, pooled, H, cls, H, s));
-  MEC_TRY(launch_head7(pooled, B, H, WcT, bc, logits, probs, s));
+  MEC_TRY(launch_head7(pooled, NS, H, WcT, bc, logits, probs, s));
   return 0;
 }
 

@@ -398,17 +398,21 @@ __global__ __launch_bounds__(256) static __attribute__((unused)) void avgpool_f3
 // src[i] + b * sstride[i] to dst[i] + b * bytes[i] (bytes % 4 == 0). BERT's last layer runs on the
 // [CLS] rows only (bert_cls_last): this packs those rows of the residual stream / GEMM operand
 // planes / LayerNorm stats into dense [B, .] buffers. Grid B, 256 threads.
+// idx (device, [B]) or null: the source row of output row b is idx[b] instead of b (the packed text
+// path: sample b's [CLS] slot, sstride then being the stride of one slot).
 struct RowGather {
   const char* src[4];
   char* dst[4];
   long long sstride[4];
   int bytes[4];
   int n;
+  const int32_t* idx;
 };
 __global__ __launch_bounds__(256) static __attribute__((unused)) void gather_rows_kernel(const RowGather g) {
   const int b = blockIdx.x;
+  const int sb = g.idx ? g.idx[b] : b;
   for (int i = 0; i < g.n; ++i) {
-    const uint32_t* s = reinterpret_cast<const uint32_t*>(g.src[i] + (size_t)b * g.sstride[i]);
+    const uint32_t* s = reinterpret_cast<const uint32_t*>(g.src[i] + (size_t)sb * g.sstride[i]);
     uint32_t* d = reinterpret_cast<uint32_t*>(g.dst[i] + (size_t)b * g.bytes[i]);
     for (int w = threadIdx.x; w < g.bytes[i] / 4; w += 256) d[w] = s[w];
   }
@@ -420,6 +424,31 @@ static inline int launch_gather_rows(const RowGather& g, int B, hipStream_t s) {
   hipLaunchKernelGGL(gather_rows_kernel, dim3(B), dim3(256), 0, s, g);
   MEC_LAUNCH_CHECK();
   return 0;
+}
+
+// The additive attention-mask term of BERT's attention kernels, staged in LDS per (row, head).
+// PACK = 0: the 128 keys' biases from the int32 mask (0 or finfo(f32).min) in sBias[128].
+// PACK = 1 (several sentences share the row, mec_text_fwd_packed): `mask` is the row's 128 uint8
+// segment ids read as 32 dwords into the first 128 bytes of sBias; a key counts only when its
+// segment is the query's own (a block-diagonal bias), so the term is 0 or finfo(f32).min as before.
+constexpr float kMaskMin = -3.4028234663852886e38f;  // finfo(f32).min
+template <int PACK>
+__device__ __forceinline__ void stage_mask(float* sBias, const int32_t* __restrict__ mask, int b, int tid) {
+  if constexpr (PACK) {
+    if (tid < 32) reinterpret_cast<int32_t*>(sBias)[tid] = mask[(size_t)b * 32 + tid];
+  } else {
+    if (tid < 128) sBias[tid] = mask[(size_t)b * 128 + tid] ? 0.f : kMaskMin;
+  }
+}
+template <int PACK>
+__device__ __forceinline__ int mask_qseg(const float* sBias, int slot) {  // after the staging barrier
+  if constexpr (PACK) return reinterpret_cast<const uint8_t*>(sBias)[slot];
+  else return 0;
+}
+template <int PACK>
+__device__ __forceinline__ float mask_term(const float* sBias, int key, int qseg) {
+  if constexpr (PACK) return reinterpret_cast<const uint8_t*>(sBias)[key] == qseg ? 0.f : kMaskMin;
+  else return sBias[key];
 }
 
 }  // namespace mec

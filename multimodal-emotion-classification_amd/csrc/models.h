@@ -86,6 +86,24 @@ int fuse_weighted(const float* s, const float* t, const float* i, int B, double*
 int fuse_weighted_f64(const double* s, const double* t, const double* i, int B, double* out, hipStream_t st);
 
 // ---------------------------------------------------------------- BERT-base
+// A packed batch (mec_text_fwd_packed): sample i of ns occupies slots off[i] .. off[i] + len[i] - 1 of the
+// 128-slot row row[i] (device arrays, a plan of mec_text_pack_plan).
+struct TextPack {
+  const int32_t *row, *off, *len;
+  int ns;
+};
+// What the pack kernel writes, carved from the forward's workspace after its other buffers: per slot the
+// token id, position id and uint8 segment id, per sample its [CLS] slot (row * 128 + off).
+struct PackBufs {
+  int32_t *ids = nullptr, *pos = nullptr, *cidx = nullptr;
+  uint8_t* seg = nullptr;
+  void take(Carver& c, int M, int ns) {
+    ids = c.take<int32_t>((size_t)M);
+    pos = c.take<int32_t>((size_t)M);
+    seg = c.take<uint8_t>((size_t)M);
+    cidx = c.take<int32_t>((size_t)ns);
+  }
+};
 struct TextModel : Model {
   DevBuf emb;      // fp32 word | pos | type | ln_g | ln_b
   DevBuf wts;      // f16 per layer: Wqkv[2304x768] Wo[768x768] Wi[3072x768] Wo2[768x3072]
@@ -93,10 +111,14 @@ struct TextModel : Model {
   DevBuf wts32;    // fp32 path: the same GEMM weights in f32
   DevBuf ws;       // workspace
   int create(const float* blob, size_t n);
+  // pk (or null): the packed form -- B packed rows holding pk->ns samples, mask unused; outputs [ns, .]
   int forward(const int32_t* ids, const int32_t* mask, int B, int L, float* cls, float* logits,
-              float* probs, hipStream_t s);
+              float* probs, hipStream_t s, const TextPack* pk = nullptr);
+  // ids int32 [B, 128] (padded layout), plan row / off / len [B] over Bp rows -> outputs in sample order
+  int forward_packed(const int32_t* ids, const int32_t* row, const int32_t* off, const int32_t* len, int B, int Bp,
+                     float* cls, float* logits, float* probs, hipStream_t s);
   int forward_f32(const int32_t* ids, const int32_t* mask, int B, int L, float* cls, float* logits,
-                  float* probs, hipStream_t s);  // bert_f32.hip
+                  float* probs, hipStream_t s, const TextPack* pk = nullptr);  // bert_f32.hip
   // fp32x3 path: wts holds the hi planes, then the lo planes (at x3_lo halfs); per GEMM B matrix
   // (4 per layer) the epilogue scale 2^-e of its planes
   size_t x3_lo = 0;
@@ -109,30 +131,38 @@ struct TextModel : Model {
   std::vector<int> x3_s_ln1, x3_s_ln2, x3_s_q, x3_s_k, x3_s_v, x3_s_ffn;
   DevBuf x3b;
   int forward_x3(const int32_t* ids, const int32_t* mask, int B, int L, float* cls, float* logits,
-                 float* probs, hipStream_t s);  // bert_f32.hip
+                 float* probs, hipStream_t s, const TextPack* pk = nullptr);  // bert_f32.hip
 };
+// The pack kernel (bert.hip): the slots' ids / position ids / segment ids over Bp rows and the samples'
+// [CLS] slots, from the padded ids [ns, 128] and the plan
+int launch_bert_pack(const int32_t* ids, const TextPack& pk, int Bp, int32_t* pids, int32_t* ppos, uint8_t* seg,
+                     int32_t* cidx, hipStream_t s);
 // lo != 0 (fp32x3 path): h16 is written as a hi plane and h16 + lo as the lo plane f16(y - hi)
 // (planes of y up: up = 2^s, the planes' activation scale, activation_exp)
+// posid (or null): per-row position ids in place of row % L (the packed path)
 int launch_bert_embed_ln(const int32_t* ids, int M, int L, const float* emb, float* h32, f16* h16, hipStream_t s,
-                         long long lo = 0, float up = 1.f);
+                         long long lo = 0, float up = 1.f, const int32_t* posid = nullptr);
 int launch_bert_layernorm(const float* x, int M, const float* g, const float* b, float* h32, f16* h16, float2* stats,
                           hipStream_t s, long long lo = 0, float up = 1.f);
 // fp32x3 attention (bert.hip): Q|K|V as f16 hi / lo planes [B*128, 2304] (lo at qkv + lo) of q 2^s_q,
 // k 2^s_k, v 2^s_v; ctx 2^s_v written as hi / lo planes [B*128, 768] (lo at ctx + clo); qks = 1/8
 // 2^-(s_q + s_k) (the scores' scale)
+// packed: mask holds the rows' uint8 segment ids (block_ops.h stage_mask) and B counts packed rows
 int launch_bert_attention_x3(const f16* qkv, long long lo, const int32_t* mask, f16* ctx, long long clo, int B,
-                             float qks, hipStream_t s);
+                             float qks, hipStream_t s, bool packed = false);
 // its [CLS]-only form (bert_cls_last): K | V planes [B*128, 1536] (lo at kv + lo), the [CLS] query
 // planes [B, 768] (lo at qc + qclo), the [CLS] context planes [B, 768] (lo at ctx + clo)
+// cidx (or null): the packed form -- B samples, sample b's [CLS] slot cidx[b], mask = segment ids
 int launch_bert_attention_x3_cls(const f16* kv, long long lo, const int32_t* mask, const f16* qc, long long qclo,
-                                 f16* ctx, long long clo, int B, float qks, hipStream_t s);
+                                 f16* ctx, long long clo, int B, float qks, hipStream_t s,
+                                 const int32_t* cidx = nullptr);
 
 // fp32x3 QKV projection + attention of one (sequence, head pair) per workgroup (bert.hip, L = 128):
 // h planes [B*128, 768] (lo at hs + hlo), Wqkv planes (lo at wqkv + wlo, epilogue scale oscale) ->
 // ctx planes [B*128, 768] (lo at ctx + clo); Q / K / V never reach HBM
 int launch_bert_qkv_attn_x3(const f16* hs, long long hlo, const f16* wqkv, long long wlo, float oscale,
                             const float* bqkv, const int32_t* mask, f16* ctx, long long clo, int B, float qks,
-                            hipStream_t s);
+                            hipStream_t s, bool packed = false);
 
 // Split n fp32 weights into f16 planes for the fp32x3 path: hi = f16(w 2^e), lo = f16(w 2^e - hi)
 // with e the largest power of two keeping max |w| 2^e <= 2^14 (so hi never overflows and lo

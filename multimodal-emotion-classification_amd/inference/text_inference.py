@@ -143,25 +143,39 @@ class TextInference:
             self._fast = _local_tokenizer(fast=True) or self.tokenizer
         return encode_batch(self._fast or self.tokenizer, texts)
 
-    def predict_texts(self, texts) -> List[Dict]:
-        """Batched `predict`: one tokenizer call and one BERT forward for all texts."""
+    def predict_texts(self, texts, pack: bool = False) -> List[Dict]:
+        """Batched `predict`: one tokenizer call and one BERT forward for all texts.
+
+        pack=True: short sentences share 128-token rows (engine.TextEncoder.forward_packed; the lengths
+        come from the tokenizer's mask on the host), so the encoder runs over fewer rows; the same
+        answers to the handle's rounding. Off by default: the padded path's outputs stay bit for bit."""
         texts = list(texts)
         if self.model is None or self.tokenizer is None:
             return [self._keyword_heuristic(t) for t in texts]
         if not texts:
             return []
         ids, mask = self.encode_batch(texts)
-        _, _, probs = self.model.checked('forward', engine.to_device(ids, self.device),
-                                         engine.to_device(mask, self.device))
+        if pack:
+            _, _, probs = self.model.checked('forward_packed', engine.to_device(ids, self.device),
+                                             engine.to_device(mask, self.device), mask.sum(1).astype(np.int32))
+        else:
+            _, _, probs = self.model.checked('forward', engine.to_device(ids, self.device),
+                                             engine.to_device(mask, self.device))
         probs = probs.cpu().numpy()
         return [self._as_dict(self.emotions, p) for p in probs]
 
-    def predict_batch(self, ids, mask):
+    def predict_batch(self, ids, mask, pack: bool = False):
         """ids/mask: device int32 [B,128] -> (cls [B,768], logits [B,7], probs [B,7]). Asynchronous on the
         current stream, except on an fp32x3 handle: there it synchronizes and checks, so a batch outside
-        the planes' range is answered by the fp32 engine (engine.HipModel.checked)."""
+        the planes' range is answered by the fp32 engine (engine.HipModel.checked).
+        pack=True: the packed path (engine.TextEncoder.forward_packed; `mask` must be a prefix mask, and
+        reading the lengths from it costs one device-to-host copy)."""
         if self.model is None:
             raise RuntimeError('text model not loaded')
+        if pack:
+            if self.model.precision == 'fp32x3':
+                return self.model.checked('forward_packed', ids, mask)
+            return self.model.forward_packed(ids, mask)
         if self.model.precision == 'fp32x3':
             return self.model.checked('forward', ids, mask, True)
         return self.model.forward(ids, mask, check_ids=True)

@@ -250,6 +250,64 @@ class TextEncoder(HipModel):
                                              _ptr(probs), _stream(self.device)), 'mec_text_fwd')
         return cls, logits, probs
 
+    packed_rows = 0  # Bp of the last forward_packed plan
+
+    def pack_plan(self, lens):
+        """The first-fit-decreasing plan of mec_text_pack_plan for host lengths `lens` (each in [1,128])
+        -> (row int32 [B], off int32 [B], Bp). Host only."""
+        lens = np.ascontiguousarray(lens, dtype=np.int32)
+        if lens.ndim != 1:
+            raise ValueError('lens: expected a 1-d array of B lengths')
+        if lens.size and (int(lens.min()) < 1 or int(lens.max()) > 128):
+            raise ValueError(f'lens: every length must be in [1,128], got min {int(lens.min())}, max {int(lens.max())}')
+        row, off = np.zeros(lens.size, np.int32), np.zeros(lens.size, np.int32)
+        ip = ctypes.POINTER(ctypes.c_int32)
+        bp = self.lib.mec_text_pack_plan(lens.ctypes.data_as(ip), int(lens.size), row.ctypes.data_as(ip),
+                                         off.ctypes.data_as(ip))
+        if bp < 0:
+            _lib.check(bp, 'mec_text_pack_plan')
+        return row, off, int(bp)
+
+    def forward_packed(self, ids: torch.Tensor, mask: torch.Tensor | None = None, lens=None):
+        """`forward` for short sentences: the B sentences share Bp <= B 128-slot rows (mec_text_fwd_packed),
+        so the encoder does Bp / B of the padded batch's work. ids int32 [B,128] in the padded layout
+        (a sentence's tokens first); its lengths come from `lens` (a host int array, what the tokenizer
+        knows) or, without it, from `mask` (int32 [B,128], which must be a prefix mask: ones, then zeros;
+        one device-to-host copy). Outputs as `forward`, in sample order; to the precision's rounding the
+        values `forward(ids, prefix mask)` gives. `packed_rows` holds the plan's Bp afterwards. The GEMM
+        shapes follow Bp, so a new Bp autotunes its own tiles."""
+        if ids.dim() != 2 or ids.shape[1] != 128:
+            raise ValueError('ids: expected [B, 128] (padding=max_length, Config.MAX_TEXT_LENGTH)')
+        B = int(ids.shape[0])
+        _check_tensor('ids', ids, torch.int32, (B, 128), self.device)
+        if mask is not None:
+            _check_tensor('mask', mask, torch.int32, (B, 128), self.device)
+        if lens is None:
+            if mask is None:
+                raise ValueError('forward_packed: pass lens (host lengths) or mask')
+            ar = torch.arange(128, device=self.device, dtype=torch.int32)
+            n = mask.sum(1, dtype=torch.int32)
+            prefix = (mask == (ar[None, :] < n[:, None]).to(torch.int32)).all(1)
+            host = torch.stack([n, prefix.to(torch.int32)]).cpu().numpy()  # the one device-to-host copy
+            if not host[1].all():
+                raise ValueError('mask: forward_packed needs a prefix mask (ones, then zeros) in every row')
+            lens = host[0]
+        lens = np.ascontiguousarray(lens, dtype=np.int32)
+        if lens.shape != (B,):
+            raise ValueError(f'lens: shape {lens.shape}, expected ({B},)')
+        row, off, bp = self.pack_plan(lens)
+        self.packed_rows = bp
+        cls, logits, probs = self._empty(B, 768), self._empty(B, 7), self._empty(B, 7)
+        if B == 0:
+            return cls, logits, probs
+        plan = torch.from_numpy(np.stack([row, off, lens])).to(self.device)  # one upload: row | off | len
+        with self._lock:
+            _lib.check(self.lib.mec_text_fwd_packed(self.handle, _ptr(ids), _ptr(plan[0]), _ptr(plan[1]),
+                                                    _ptr(plan[2]), B, bp, _ptr(cls), _ptr(logits), _ptr(probs),
+                                                    _stream(self.device)), 'mec_text_fwd_packed')
+        plan.record_stream(torch.cuda.current_stream(self.device))
+        return cls, logits, probs
+
 
 class LstmTextEncoder(HipModel):
     """The reference's BiLSTM text model (model_training/train_lstm_text_model.py:96-120) on the HIP
@@ -445,7 +503,7 @@ class FusedPipeline:
         # ahead of the image stream's and the image kernels fill the CUs BERT leaves idle
         self._text = (torch.cuda.Stream(device=self.device, priority=0 if image_priority else -1)
                       if (concurrent and (text_priority or image_priority)) else None)
-        self._tuned = set()  # batch sizes whose GEMM shapes were autotuned (serially)
+        self._tuned = set()  # batch sizes B, or (B, packed rows Bp), whose GEMM shapes were autotuned (serially)
         self._last, self._since_check = None, 0
         if concurrent and precision == 'f16':
             # BERT FFN2 (M = 128 B, N = 768, K = 3072) on the 256 x 256 ping-pong tile beside the
@@ -470,21 +528,32 @@ class FusedPipeline:
             # 25.95 / 25.86 (profiles/r03_ab_x3tag_qkv.txt)
             self.text.set_option('gemm_x3_tag', TAG_BERT_QKV * 100000 + 70256)
 
-    def forward(self, x_speech, ids, mask, gray, epilogue=None):
+    def forward(self, x_speech, ids, mask, gray, epilogue=None, text_lens=None):
         """One batch through the path -> dict of per-modality and fusion outputs (and, with
-        `epilogue`, ``(outputs, epilogue(outputs))``, the callable run on the fusion's stream)."""
+        `epilogue`, ``(outputs, epilogue(outputs))``, the callable run on the fusion's stream).
+
+        text_lens (a host int array of the B sentence lengths, each in [1,128]; None = the padded path):
+        the text leg runs packed (TextEncoder.forward_packed) on the text stream. The plan's Bp sets
+        BERT's GEMM shapes (M = 128 Bp), so the serial first-batch autotune rule applies per (B, Bp): the
+        first batch of a Bp not seen with this B runs serially."""
         main = torch.cuda.current_stream(self.device)
         B = int(ids.shape[0])
-        if not self.concurrent or B not in self._tuned:
+        if text_lens is None:
+            text_fwd, key = (lambda: self.text.forward(ids, mask)), B
+        else:
+            text_lens = np.ascontiguousarray(text_lens, dtype=np.int32)
+            key = (B, self.text.pack_plan(text_lens)[2])
+            text_fwd = lambda: self.text.forward_packed(ids, mask, text_lens)  # noqa: E731
+        if not self.concurrent or key not in self._tuned:
             # a batch size not seen yet runs serially on one stream, so each new GEMM shape is
             # autotuned alone (not against the other encoder's kernels)
             for st in (self._side, self._text, self._tail):  # nothing else in flight while tuning
                 if st is not None:
                     main.wait_stream(st)
             sf, sl, sp = self.speech.forward(x_speech)
-            tf, tl, tp = self.text.forward(ids, mask)
+            tf, tl, tp = text_fwd()
             imf, il, ip = self.image.forward(gray)
-            self._tuned.add(B)
+            self._tuned.add(key)
             fstream = main
         else:
             side = self._side
@@ -496,7 +565,7 @@ class FusedPipeline:
                 tstream = self._text
                 tstream.wait_stream(main)
                 with torch.cuda.stream(tstream):
-                    tf, tl, tp = self.text.forward(ids, mask)
+                    tf, tl, tp = text_fwd()
                 for t in (ids, mask):
                     t.record_stream(tstream)
                 if not self.pipelined:
@@ -505,7 +574,7 @@ class FusedPipeline:
                         t.record_stream(main)
             else:
                 tstream = main
-                tf, tl, tp = self.text.forward(ids, mask)
+                tf, tl, tp = text_fwd()
             for t in (x_speech, gray):
                 t.record_stream(side)
             if self.pipelined:
@@ -525,6 +594,8 @@ class FusedPipeline:
                    'fusion': (fl, fp, aw, dw)}
             extra = epilogue(out) if epilogue is not None else None
         self._last = {'text': (ids, mask), 'image': (gray,), 'out': out}  # check() repairs this batch
+        if text_lens is not None:
+            self._last.update(text=(ids, mask, text_lens), text_method='forward_packed')
         self._since_check += 1
         return out if epilogue is None else (out, extra)
 
@@ -546,7 +617,7 @@ class FusedPipeline:
         self._since_check = 0
         for name, m in (('text', self.text), ('image', self.image)):
             if last is not None and n == 1 and m.precision == 'fp32x3':
-                if m.recover('forward', last[name], last['out'][name]):
+                if m.recover(last.get(name + '_method', 'forward'), last[name], last['out'][name]):
                     redo.append(name)
             else:
                 m.check()
