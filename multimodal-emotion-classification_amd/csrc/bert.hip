@@ -17,13 +17,9 @@
 // per LayerNorm.
 // Head: cls = h32[:,0,:] (pre-pooler CLS feature, text_inference.py:125);
 //       probs = softmax(Wc tanh(Wp cls + bp) + bc).
-#include "block_ops.h"
-#include "models.h"
+#include "bert_model.h"
 
 namespace mec {
-
-constexpr int BH = 768, BI = 3072, BHEADS = 12, BDH = 64, BLAYERS = 12, BVOCAB = 30522, BMAXPOS = 512;
-constexpr int ATT_L = 128;  // the sequence length every kernel here is built for
 
 // ----------------------------------------------------------------------------- embed+LN
 // One wave per token row; each lane owns 12 of the 768 features (3 float4).
@@ -1056,12 +1052,51 @@ int launch_bert_qkv_attn_x3(const f16* hs, long long hlo, const f16* wqkv, long 
   return 0;
 }
 
-// ----------------------------------------------------------------------------- model
-// prm layout per layer (floats): bqkv 2304 | bo 768 | ln1g 768 | ln1b 768 | bi 3072 | bo2 768 |
-// ln2g 768 | ln2b 768  => 9984 ; then head: WpT 768*768 | bp 768 | WcT 768*7 | bc 7
-constexpr size_t PRM_LAYER = 2304 + 768 * 3 + 3072 + 768 * 3;
-constexpr size_t WT_LAYER = (size_t)2304 * 768 + 768 * 768 + 3072 * 768 + 768 * 3072;
+// ----------------------------------------------------------------------------- f16 attention launchers
+// kv: K | V of every token [rows * 128, 1536]; qc, ctx: the samples' [CLS] query / context rows [NS, 768];
+// cidx (or null): the packed form (mask = segment ids, sample b's [CLS] slot cidx[b])
+static int launch_bert_attention_cls(const f16* kv, const int32_t* mask, const f16* qc, f16* ctx, int NS, hipStream_t s,
+                                     const int32_t* cidx) {
+  if (cidx)
+    hipLaunchKernelGGL(bert_attention_cls_kernel<1>, dim3(NS * BHEADS), dim3(256), 0, s, kv, mask, qc, ctx, cidx);
+  else
+    hipLaunchKernelGGL(bert_attention_cls_kernel<0>, dim3(NS * BHEADS), dim3(256), 0, s, kv, mask, qc, ctx, nullptr);
+  MEC_LAUNCH_CHECK();
+  return 0;
+}
 
+// packed: mask holds the rows' uint8 segment ids and B counts packed rows (both launchers below)
+static int launch_bert_qkv_attn(const f16* h16, const f16* wqkv, const float* bqkv, const int32_t* mask, f16* ctx, int B,
+                                hipStream_t s, bool packed) {
+#ifdef MEC_PROBES
+  if (opt().bert_qkv_attn == 2)
+    hipLaunchKernelGGL((bert_qkv_attn_kernel<1>), dim3(B * 6), dim3(512), 0, s, h16, wqkv, bqkv, mask, ctx, B);
+  else if (opt().bert_qkv_attn == 3)
+    hipLaunchKernelGGL((bert_qkv_attn_kernel<2>), dim3(B * 6), dim3(512), 0, s, h16, wqkv, bqkv, mask, ctx, B);
+  else
+#endif
+  if (opt().bert_qkv_attn_heads == 1 && packed)
+    hipLaunchKernelGGL((bert_qkv_attn_kernel<0, 1, 1>), dim3(B * 12), dim3(256), 0, s, h16, wqkv, bqkv, mask, ctx, B);
+  else if (packed)
+    hipLaunchKernelGGL((bert_qkv_attn_kernel<0, 2, 1>), dim3(B * 6), dim3(512), 0, s, h16, wqkv, bqkv, mask, ctx, B);
+  else if (opt().bert_qkv_attn_heads == 1)
+    hipLaunchKernelGGL((bert_qkv_attn_kernel<0, 1>), dim3(B * 12), dim3(256), 0, s, h16, wqkv, bqkv, mask, ctx, B);
+  else
+    hipLaunchKernelGGL((bert_qkv_attn_kernel<0>), dim3(B * 6), dim3(512), 0, s, h16, wqkv, bqkv, mask, ctx, B);
+  MEC_LAUNCH_CHECK();
+  return 0;
+}
+
+static int launch_bert_attention(const f16* qkv, const int32_t* mask, f16* ctx, int B, hipStream_t s, bool packed) {
+  if (packed)
+    hipLaunchKernelGGL(bert_attention_kernel<1>, dim3(B * BHEADS), dim3(256), 0, s, qkv, mask, ctx);
+  else
+    hipLaunchKernelGGL(bert_attention_kernel<0>, dim3(B * BHEADS), dim3(256), 0, s, qkv, mask, ctx);
+  MEC_LAUNCH_CHECK();
+  return 0;
+}
+
+// ----------------------------------------------------------------------------- model
 static void to_f16(std::vector<f16>& dst, size_t off, const float* src, size_t n) {
   for (size_t i = 0; i < n; ++i) dst[off + i] = (f16)src[i];
 }
@@ -1085,48 +1120,48 @@ int TextModel::create(const float* blob, size_t n) {
   const bool f32 = prec != PREC_F16;
   std::vector<f16> w(f32 ? 0 : WT_LAYER * BLAYERS);
   std::vector<float> w32(f32 ? WT_LAYER * BLAYERS : 0);
-  auto put = [&](size_t off, const float* src, size_t cnt) {
-    if (f32) std::copy(src, src + cnt, w32.begin() + off);
-    else to_f16(w, off, src, cnt);
+  // the next cnt blob floats -> matrix m of layer l (WT_OFF), from its element `off` on
+  auto put = [&](int l, int m, size_t off, size_t cnt) {
+    const float* src = rd.take(cnt);
+    const size_t at = WT_LAYER * l + WT_OFF[m] + off;
+    if (f32) std::copy(src, src + cnt, w32.begin() + at);
+    else to_f16(w, at, src, cnt);
   };
-  std::vector<float> pr(PRM_LAYER * BLAYERS + (size_t)BH * BH + BH + BH * 7 + 7);
+  auto take_to = [&](float* dst, size_t cnt) {
+    const float* x = rd.take(cnt);
+    std::copy(x, x + cnt, dst);
+  };
+  std::vector<float> pr(PRM_FLOATS);
   for (int l = 0; l < BLAYERS; ++l) {
-    f16* dummy = nullptr;
-    (void)dummy;
-    const size_t wo = WT_LAYER * l;
-    const size_t po = PRM_LAYER * l;
+    const LayerParams<float> p = layer_params(pr.data(), l);
     // Wqkv rows: query | key | value (torch Linear weight [out,in] = GEMM B [N,K])
     for (int q = 0; q < 3; ++q) {
-      put(wo + (size_t)q * BH * BH, rd.take((size_t)BH * BH), (size_t)BH * BH);
-      const float* bb = rd.take(BH);
-      std::copy(bb, bb + BH, pr.begin() + po + q * BH);
+      put(l, 0, (size_t)q * BH * BH, (size_t)BH * BH);
+      take_to(p.bqkv + q * BH, BH);
     }
-    put(wo + (size_t)2304 * BH, rd.take((size_t)BH * BH), (size_t)BH * BH);
-    { const float* x = rd.take(BH); std::copy(x, x + BH, pr.begin() + po + 2304); }
-    { const float* x = rd.take(BH); std::copy(x, x + BH, pr.begin() + po + 2304 + 768); }
-    { const float* x = rd.take(BH); std::copy(x, x + BH, pr.begin() + po + 2304 + 1536); }
-    put(wo + (size_t)2304 * BH + BH * BH, rd.take((size_t)BI * BH), (size_t)BI * BH);
-    { const float* x = rd.take(BI); std::copy(x, x + BI, pr.begin() + po + 2304 + 2304); }
-    put(wo + (size_t)2304 * BH + BH * BH + (size_t)BI * BH, rd.take((size_t)BH * BI), (size_t)BH * BI);
-    { const float* x = rd.take(BH); std::copy(x, x + BH, pr.begin() + po + 2304 + 2304 + 3072); }
-    { const float* x = rd.take(BH); std::copy(x, x + BH, pr.begin() + po + 2304 + 2304 + 3072 + 768); }
-    { const float* x = rd.take(BH); std::copy(x, x + BH, pr.begin() + po + 2304 + 2304 + 3072 + 1536); }
+    put(l, 1, 0, WT_SIZE[1]);
+    take_to(p.bo, BH);
+    take_to(p.g1, BH);
+    take_to(p.b1, BH);
+    put(l, 2, 0, WT_SIZE[2]);
+    take_to(p.bi, BI);
+    put(l, 3, 0, WT_SIZE[3]);
+    take_to(p.bo2, BH);
+    take_to(p.g2, BH);
+    take_to(p.b2, BH);
   }
-  size_t ho = PRM_LAYER * BLAYERS;
+  float* head = pr.data() + PRM_LAYER * BLAYERS;
   const float* wp = rd.take((size_t)BH * BH);
   const float* bp = rd.take(BH);
-  const float* wc = rd.take((size_t)7 * BH);
-  const float* bc = rd.take(7);
+  const float* wc = rd.take((size_t)BCLASSES * BH);
+  const float* bc = rd.take(BCLASSES);
   MEC_REQUIRE(rd.ok && rd.off == n, "text blob size mismatch");
   for (int i = 0; i < BH; ++i)
-    for (int j = 0; j < BH; ++j) pr[ho + (size_t)i * BH + j] = wp[(size_t)j * BH + i];
-  ho += (size_t)BH * BH;
-  std::copy(bp, bp + BH, pr.begin() + ho);
-  ho += BH;
+    for (int j = 0; j < BH; ++j) head[HO_WPT + (size_t)i * BH + j] = wp[(size_t)j * BH + i];
+  std::copy(bp, bp + BH, head + HO_BP);
   for (int i = 0; i < BH; ++i)
-    for (int j = 0; j < 7; ++j) pr[ho + (size_t)i * 7 + j] = wc[(size_t)j * BH + i];
-  ho += (size_t)BH * 7;
-  std::copy(bc, bc + 7, pr.begin() + ho);
+    for (int j = 0; j < BCLASSES; ++j) head[HO_WCT + (size_t)i * BCLASSES + j] = wc[(size_t)j * BH + i];
+  std::copy(bc, bc + BCLASSES, head + HO_BC);
   MEC_TRY(upload(emb, e.data(), e.size() * sizeof(float)));
   if (prec == PREC_FP32X3) {
     // Activation-plane exponents from rigorous bounds (activation_exp, target 2^15, so no plane can
@@ -1162,63 +1197,52 @@ int TextModel::create(const float* blob, size_t n) {
     double b_in = ln_bound(lg, lb);
     x3_s_emb = aexp(b_in, kX3BoundTarget);
     x3_note("emb_ln", x3_s_emb, b_in);
-    std::vector<int> s_in(BLAYERS);
-    x3_s_ln1.assign(BLAYERS, 0);
-    x3_s_ln2.assign(BLAYERS, 0);
-    x3_s_q.assign(BLAYERS, 0);
-    x3_s_k.assign(BLAYERS, 0);
-    x3_s_v.assign(BLAYERS, 0);
-    x3_s_ffn.assign(BLAYERS, 0);
-    std::vector<float> bq((size_t)2304 * BLAYERS);
+    x3_layers.assign(BLAYERS, X3Layer());
+    std::vector<float> bq((size_t)BQKV * BLAYERS);
+    const size_t total = WT_LAYER * BLAYERS;
+    std::vector<f16> hl(2 * total);
+    x3_lo = total;
     for (int l = 0; l < BLAYERS; ++l) {
-      float* wl = w32.data() + WT_LAYER * l;
-      const float* pl = pr.data() + PRM_LAYER * l;
-      s_in[l] = l ? x3_s_ln2[l - 1] : x3_s_emb;
+      X3Layer& x = x3_layers[l];
+      const LayerWeights<float> wl = layer_weights(w32.data(), l);
+      const LayerParams<const float> pl = layer_params<const float>(pr.data(), l);
+      const int s_in = l ? x3_layers[l - 1].s_ln2 : x3_s_emb;
       int sqkv[3];
       double bqkv3[3];
       for (int q = 0; q < 3; ++q) {
-        bqkv3[q] = proj_bound(b_in, wl + (size_t)q * BH * BH, pl + q * BH, BH, BH);
+        bqkv3[q] = proj_bound(b_in, wl.wqkv + (size_t)q * BH * BH, pl.bqkv + q * BH, BH, BH);
         sqkv[q] = aexp(bqkv3[q], kX3BoundTarget);
       }
-      const double b1 = ln_bound(pl + 3072, pl + 3840);
-      x3_s_ln1[l] = aexp(b1, kX3BoundTarget);
-      const double bffn = proj_bound(b1, wl + (size_t)2304 * BH + BH * BH, pl + 4608, BI, BH);
-      x3_s_ffn[l] = aexp(bffn, kX3BoundTarget);
-      b_in = ln_bound(pl + 8448, pl + 9216);
-      x3_s_ln2[l] = aexp(b_in, kX3BoundTarget);
+      const double b1 = ln_bound(pl.g1, pl.b1);
+      x.s_ln1 = aexp(b1, kX3BoundTarget);
+      const double bffn = proj_bound(b1, wl.wi, pl.bi, BI, BH);
+      x.s_ffn = aexp(bffn, kX3BoundTarget);
+      b_in = ln_bound(pl.g2, pl.b2);
+      x.s_ln2 = aexp(b_in, kX3BoundTarget);
       const std::string ln = "layer" + std::to_string(l) + ".";
       x3_note(ln + "q", sqkv[0], bqkv3[0]);
       x3_note(ln + "k", sqkv[1], bqkv3[1]);
       x3_note(ln + "v", sqkv[2], bqkv3[2]);
-      x3_note(ln + "ln1", x3_s_ln1[l], b1);
-      x3_note(ln + "ffn", x3_s_ffn[l], bffn);
-      x3_note(ln + "ln2", x3_s_ln2[l], b_in);
-      x3_s_q[l] = sqkv[0];
-      x3_s_k[l] = sqkv[1];
-      x3_s_v[l] = sqkv[2];
+      x3_note(ln + "ln1", x.s_ln1, b1);
+      x3_note(ln + "ffn", x.s_ffn, bffn);
+      x3_note(ln + "ln2", x.s_ln2, b_in);
+      x.s_q = sqkv[0];
+      x.s_k = sqkv[1];
+      x.s_v = sqkv[2];
       for (int q = 0; q < 3; ++q) {
-        for (size_t i = 0; i < (size_t)BH * BH; ++i) wl[(size_t)q * BH * BH + i] = std::ldexp(wl[(size_t)q * BH * BH + i], sqkv[q]);
-        for (int j = 0; j < BH; ++j) bq[(size_t)2304 * l + q * BH + j] = std::ldexp(pl[q * BH + j], sqkv[q]);
+        float* wq = wl.wqkv + (size_t)q * BH * BH;
+        for (size_t i = 0; i < (size_t)BH * BH; ++i) wq[i] = std::ldexp(wq[i], sqkv[q]);
+        for (int j = 0; j < BH; ++j) bq[(size_t)BQKV * l + q * BH + j] = std::ldexp(pl.bqkv[q * BH + j], sqkv[q]);
       }
-    }
-    // each GEMM's B matrix (Wqkv | Wo | Wi | Wo2 of a layer) scaled by 2^e (max |w| 2^e <= 2^14,
-    // exact) and split into hi = f16(w 2^e) and lo = f16(w 2^e - hi) planes; the GEMM epilogue
-    // multiplies the accumulator by 2^-e and the activation-plane factors (GemmParams::oscale)
-    const size_t total = WT_LAYER * BLAYERS;
-    std::vector<f16> hl(2 * total);
-    x3_lo = total;
-    x3_scale.assign(4 * BLAYERS, 1.f);
-    const size_t sizes[4] = {(size_t)2304 * BH, (size_t)BH * BH, (size_t)BI * BH, (size_t)BH * BI};
-    for (int l = 0; l < BLAYERS; ++l) {
-      size_t off = WT_LAYER * l;
-      for (int mtx = 0; mtx < 4; ++mtx) {
-        x3_scale[4 * l + mtx] = split_planes(w32.data() + off, sizes[mtx], hl.data() + off, hl.data() + total + off);
-        off += sizes[mtx];
+      // each GEMM's B matrix (Wqkv | Wo | Wi | Wo2 of a layer) scaled by 2^e (max |w| 2^e <= 2^14,
+      // exact) and split into hi = f16(w 2^e) and lo = f16(w 2^e - hi) planes; the GEMM epilogue
+      // multiplies the accumulator by 2^-e and the activation-plane factors (GemmParams::oscale)
+      const int s_a[4] = {s_in, x.s_v, x.s_ln1, x.s_ffn};  // each GEMM's A operand planes' exponent
+      for (int m = 0; m < 4; ++m) {
+        const size_t off = WT_LAYER * l + WT_OFF[m];
+        const float e2 = split_planes(w32.data() + off, WT_SIZE[m], hl.data() + off, hl.data() + total + off);
+        x.scale[m] = std::ldexp(e2, -s_a[m]);
       }
-      x3_scale[4 * l + 0] = std::ldexp(x3_scale[4 * l + 0], -s_in[l]);
-      x3_scale[4 * l + 1] = std::ldexp(x3_scale[4 * l + 1], -x3_s_v[l]);
-      x3_scale[4 * l + 2] = std::ldexp(x3_scale[4 * l + 2], -x3_s_ln1[l]);
-      x3_scale[4 * l + 3] = std::ldexp(x3_scale[4 * l + 3], -x3_s_ffn[l]);
     }
     MEC_TRY(upload(x3b, bq.data(), bq.size() * sizeof(float)));
     MEC_TRY(upload(wts, hl.data(), hl.size() * sizeof(f16)));
@@ -1241,10 +1265,9 @@ int TextModel::forward_packed(const int32_t* ids, const int32_t* row, const int3
   return forward(ids, nullptr, Bp, ATT_L, cls, logits, probs, s, &pk);
 }
 
-// pk (or null): the packed form. B is then the number of packed rows, pk->ns the number of samples; the
-// pack kernel builds the slots' ids, position ids and segment ids (which take the mask's place in every
-// attention kernel) and the samples' [CLS] slots, which the [CLS]-row gathers and the [CLS]-only attention
-// read. Every buffer over token rows keeps M = B * 128; every compact [CLS]-row buffer has ns rows.
+// pk (or null): the packed form. B is then the number of packed rows, pk->ns the number of samples
+// (bert_model.h TextBatch). Every buffer over token rows keeps M = B * 128; every compact [CLS]-row buffer
+// has ns rows.
 int TextModel::forward(const int32_t* ids, const int32_t* mask, int B, int L, float* cls, float* logits,
                        float* probs, hipStream_t s, const TextPack* pk) {
   MEC_REQUIRE(B >= 0, "text: B < 0");
@@ -1253,182 +1276,100 @@ int TextModel::forward(const int32_t* ids, const int32_t* mask, int B, int L, fl
   MEC_REQUIRE(ids && (mask || pk) && cls && logits && probs, "text: null pointer");
   if (prec == PREC_FP32) return forward_f32(ids, mask, B, L, cls, logits, probs, s, pk);
   if (prec == PREC_FP32X3) return forward_x3(ids, mask, B, L, cls, logits, probs, s, pk);
-  const int M = B * L;
-  const int NS = pk ? pk->ns : B;  // samples: rows of the compact [CLS] buffers and of the outputs
   // workspace: h32 | t32 (f32 [M,768]) ; h16 | ctx16 (f16 [M,768]) ; qkv16 [M,2304] / i16 [M,3072]
-  // + the [CLS]-row buffers of the last layer (bert_cls_last): h32c | t32c (f32 [B,768]) ; h16c | qc |
-  // ctxc (f16 [B,768]) ; fc (f16 [B,3072]) ; st1c | st2c ([B] float2)
+  // + the [CLS]-row buffers of the last layer (bert_cls_last): h32c | t32c (f32 [NS,768]) ; h16c | qc |
+  // ctxc (f16 [NS,768]) ; fc (f16 [NS,3072]) ; st1c | st2c ([NS] float2)
   float *h32, *t32, *pooled, *h32c, *t32c;
   f16 *h16, *ctx16, *big16, *h16c, *qc, *ctxc, *fc;
   float2 *st1, *st1c;
-  PackBufs pkb;
-  MEC_TRY(carve(ws, [&](Carver& c) {
-    h32 = c.take<float>((size_t)M * BH);
-    t32 = c.take<float>((size_t)M * BH);
-    h16 = c.take<f16>((size_t)M * BH);
-    ctx16 = c.take<f16>((size_t)M * BH);
-    big16 = c.take<f16>((size_t)M * BI);  // qkv16 [M,2304] then i16 [M,3072]
-    pooled = c.take<float>((size_t)NS * BH);
-    st1 = c.take<float2>((size_t)M * 2);  // LN1 | LN2 row stats [M] each
-    h32c = c.take<float>((size_t)NS * BH);
-    t32c = c.take<float>((size_t)NS * BH);
-    h16c = c.take<f16>((size_t)NS * BH);
-    qc = c.take<f16>((size_t)NS * BH);
-    ctxc = c.take<f16>((size_t)NS * BH);
-    fc = c.take<f16>((size_t)NS * BI);
-    st1c = c.take<float2>((size_t)NS * 2);
-    if (pk) pkb.take(c, M, NS);
+  TextBatch tb;
+  MEC_TRY(text_prologue(tb, ws, ids, mask, B, pk, s, [&](Carver& c) {
+    const size_t M = tb.M, NS = tb.NS;
+    h32 = c.take<float>(M * BH);
+    t32 = c.take<float>(M * BH);
+    h16 = c.take<f16>(M * BH);
+    ctx16 = c.take<f16>(M * BH);
+    big16 = c.take<f16>(M * BI);  // qkv16 [M,2304] then i16 [M,3072]
+    pooled = c.take<float>(NS * BH);
+    st1 = c.take<float2>(M * 2);  // LN1 | LN2 row stats [M] each
+    h32c = c.take<float>(NS * BH);
+    t32c = c.take<float>(NS * BH);
+    h16c = c.take<f16>(NS * BH);
+    qc = c.take<f16>(NS * BH);
+    ctxc = c.take<f16>(NS * BH);
+    fc = c.take<f16>(NS * BI);
+    st1c = c.take<float2>(NS * 2);
   }));
+  const int M = tb.M, NS = tb.NS;
   float2* st2 = st1 + M;
   float2* st2c = st1c + NS;
   const bool cls_last = opt().bert_cls_last != 0;
-  const int32_t* posid = nullptr;
-  const int32_t* cidx = nullptr;
-  if (pk) {
-    MEC_TRY(launch_bert_pack(ids, *pk, B, pkb.ids, pkb.pos, pkb.seg, pkb.cidx, s));
-    ids = pkb.ids; posid = pkb.pos; cidx = pkb.cidx;
-    mask = reinterpret_cast<const int32_t*>(pkb.seg);
-  }
-
-  const float* E = emb.as<float>();
-  const float* word = E;
-  const float* pos = word + (size_t)BVOCAB * BH;
-  const float* type = pos + (size_t)BMAXPOS * BH;
-  const float* lng = type + 2 * BH;
-  const float* lnb = lng + BH;
-  const dim3 rows_grid((M + 3) / 4);
-  hipLaunchKernelGGL(bert_embed_ln_kernel, rows_grid, dim3(256), 0, s, ids, M, L, word, pos, type, lng, lnb, h32,
-                     h16, 0LL, 1.f, nullptr, posid);
-  MEC_LAUNCH_CHECK();
   const f16* W = wts.as<f16>();
   const float* P = prm.as<float>();
-  for (int l = 0; l < BLAYERS; ++l) {
-    const f16* wqkv = W + WT_LAYER * l;
-    const f16* wo = wqkv + (size_t)2304 * BH;
-    const f16* wi = wo + (size_t)BH * BH;
-    const f16* wo2 = wi + (size_t)BI * BH;
-    const float* pl = P + PRM_LAYER * l;
-    const float *bqkv = pl, *bo = pl + 2304, *g1 = pl + 3072, *b1 = pl + 3840, *bi = pl + 4608,
-                *bo2 = pl + 7680, *g2 = pl + 8448, *b2 = pl + 9216;
+
+  // Only the first LN (the embedding's) and the last write their f32 output. Every other residual add
+  // re-derives it from the pre-LN sum and the row stats in its GEMM epilogue (r_stats). The f32 stream
+  // ping-pongs, so no GEMM reads its own output (a launch stays idempotent: the tile autotuner re-runs
+  // candidates on the same buffers).
+  auto tail = [&](int l, const TailRows& r) -> int {
+    const LayerWeights<const f16> w = layer_weights(W, l);
+    const LayerParams<const float> p = layer_params(P, l);
+    auto tag = [&](int t) { return r.tagged ? t : (int)TAG_NONE; };
     GemmParams g;
-    if (cls_last && l == BLAYERS - 1 && l > 0) {
-      // [CLS]-only last layer: K / V for every token, everything else on the B [CLS] rows (the
+    g.A = r.ctx; g.B = w.wo; g.bias = p.bo; g.R = r.h32; g.r_f32 = 1; g.C32 = r.t32; g.M = r.n; g.N = BH; g.K = BH;
+    if (r.deferred_in) { g.r_stats = r.st2; g.r_g = layer_params(P, l - 1).g2; g.r_b = layer_params(P, l - 1).b2; }
+    MEC_TRY(launch_gemm(g, s, &prof, tag(TAG_BERT_OPROJ)));
+    MEC_TRY(prof.begin(tag(TAG_BERT_LN), s));
+    MEC_TRY(launch_bert_layernorm(r.t32, r.n, p.g1, p.b1, nullptr, r.op, r.st1, s));
+    MEC_TRY(prof.end(tag(TAG_BERT_LN), s));
+    g = GemmParams();
+    g.A = r.op; g.B = w.wi; g.bias = p.bi; g.act = ACT_GELU; g.C16 = r.ffn; g.M = r.n; g.N = BI; g.K = BH;
+    MEC_TRY(launch_gemm(g, s, &prof, tag(TAG_BERT_FFN1)));
+    g = GemmParams();
+    g.A = r.ffn; g.B = w.wo2; g.bias = p.bo2; g.R = r.t32; g.r_f32 = 1; g.r_stats = r.st1; g.r_g = p.g1; g.r_b = p.b1;
+    g.C32 = r.h32; g.M = r.n; g.N = BH; g.K = BI;
+    MEC_TRY(launch_gemm(g, s, &prof, tag(TAG_BERT_FFN2)));
+    MEC_TRY(prof.begin(tag(TAG_BERT_LN), s));
+    // in place: each wave holds its row in registers before writing it
+    MEC_TRY(launch_bert_layernorm(r.h32, r.n, p.g2, p.b2, r.full_out ? r.h32 : nullptr, r.op, r.st2, s));
+    MEC_TRY(prof.end(tag(TAG_BERT_LN), s));
+    return 0;
+  };
+
+  MEC_TRY(launch_bert_embed_ln(tb.ids, M, L, emb.as<float>(), h32, h16, s, 0, 1.f, tb.posid));
+  for (int l = 0; l < BLAYERS; ++l) {
+    const LayerWeights<const f16> w = layer_weights(W, l);
+    const LayerParams<const float> p = layer_params(P, l);
+    const bool last = l == BLAYERS - 1;
+    GemmParams g;
+    if (cls_last && last) {
+      // [CLS]-only last layer: K / V for every token, everything else on the NS [CLS] rows (the
       // pooler, logits and CLS feature read nothing else). Same kernels and expressions per row as
-      // the full layer below (its O-proj residual is the deferred LN2 of layer l-1), so same bits.
-      const float* pg2 = P + PRM_LAYER * (l - 1) + 8448;
-      RowGather rg{};
-      rg.n = 3;
-      rg.src[0] = reinterpret_cast<const char*>(h32); rg.dst[0] = reinterpret_cast<char*>(h32c);
-      const long long gs = pk ? 1 : L;  // rows between gathered rows: cidx counts slots
-      rg.idx = cidx;
-      rg.sstride[0] = gs * BH * 4; rg.bytes[0] = BH * 4;
-      rg.src[1] = reinterpret_cast<const char*>(h16); rg.dst[1] = reinterpret_cast<char*>(h16c);
-      rg.sstride[1] = gs * BH * 2; rg.bytes[1] = BH * 2;
-      rg.src[2] = reinterpret_cast<const char*>(st2); rg.dst[2] = reinterpret_cast<char*>(st2c);
-      rg.sstride[2] = gs * 8; rg.bytes[2] = 8;
-      MEC_TRY(launch_gather_rows(rg, NS, s));
-      g.A = h16; g.B = wqkv + (size_t)BH * BH; g.bias = bqkv + BH; g.C16 = big16; g.M = M; g.N = 2 * BH; g.K = BH;
+      // the full layer, so same bits.
+      MEC_TRY(gather_cls_rows(tb, {{h32, h32c, BH * 4}, {h16, h16c, BH * 2}, {st2, st2c, 8}}, s));
+      g.A = h16; g.B = w.wqkv + (size_t)BH * BH; g.bias = p.bqkv + BH; g.C16 = big16; g.M = M; g.N = 2 * BH; g.K = BH;
       MEC_TRY(launch_gemm(g, s, &prof, TAG_NONE));  // K | V [M, 1536]
       g = GemmParams();
-      g.A = h16c; g.B = wqkv; g.bias = bqkv; g.C16 = qc; g.M = NS; g.N = BH; g.K = BH;
+      g.A = h16c; g.B = w.wqkv; g.bias = p.bqkv; g.C16 = qc; g.M = NS; g.N = BH; g.K = BH;
       MEC_TRY(launch_gemm(g, s, &prof, TAG_NONE));  // Q of the [CLS] rows
-      if (pk)
-        hipLaunchKernelGGL(bert_attention_cls_kernel<1>, dim3(NS * BHEADS), dim3(256), 0, s, big16, mask, qc, ctxc, cidx);
-      else
-        hipLaunchKernelGGL(bert_attention_cls_kernel<0>, dim3(B * BHEADS), dim3(256), 0, s, big16, mask, qc, ctxc, nullptr);
-      MEC_LAUNCH_CHECK();
-      g = GemmParams();
-      g.A = ctxc; g.B = wo; g.bias = bo; g.R = h32c; g.r_f32 = 1; g.r_stats = st2c; g.r_g = pg2; g.r_b = pg2 + BH;
-      g.C32 = t32c; g.M = NS; g.N = BH; g.K = BH;
-      MEC_TRY(launch_gemm(g, s, &prof, TAG_NONE));
-      launch_ln_rows(t32c, NS, g1, b1, nullptr, h16c, st1c, s, 0, 1.f);
-      MEC_LAUNCH_CHECK();
-      g = GemmParams();
-      g.A = h16c; g.B = wi; g.bias = bi; g.act = ACT_GELU; g.C16 = fc; g.M = NS; g.N = BI; g.K = BH;
-      MEC_TRY(launch_gemm(g, s, &prof, TAG_NONE));
-      g = GemmParams();
-      g.A = fc; g.B = wo2; g.bias = bo2; g.R = t32c; g.r_f32 = 1; g.r_stats = st1c; g.r_g = g1; g.r_b = b1;
-      g.C32 = h32c; g.M = NS; g.N = BH; g.K = BI;
-      MEC_TRY(launch_gemm(g, s, &prof, TAG_NONE));
-      launch_ln_rows(h32c, NS, g2, b2, h32c, h16c, st2c, s, 0, 1.f);  // in place, written in full (the pooler's input)
-      MEC_LAUNCH_CHECK();
+      MEC_TRY(launch_bert_attention_cls(big16, tb.mask, qc, ctxc, NS, s, tb.cidx));
+      MEC_TRY(tail(l, {NS, h32c, t32c, ctxc, h16c, fc, st1c, st2c, /*deferred_in=*/true, /*full_out=*/true, /*tagged=*/false}));
       break;
     }
     if (opt().bert_qkv_attn) {
       MEC_TRY(prof.begin(TAG_BERT_ATTN, s));
-#ifdef MEC_PROBES
-      if (opt().bert_qkv_attn == 2)
-        hipLaunchKernelGGL((bert_qkv_attn_kernel<1>), dim3(B * 6), dim3(512), 0, s, h16, wqkv, bqkv, mask, ctx16, B);
-      else if (opt().bert_qkv_attn == 3)
-        hipLaunchKernelGGL((bert_qkv_attn_kernel<2>), dim3(B * 6), dim3(512), 0, s, h16, wqkv, bqkv, mask, ctx16, B);
-      else
-#endif
-      if (opt().bert_qkv_attn_heads == 1 && pk)
-        hipLaunchKernelGGL((bert_qkv_attn_kernel<0, 1, 1>), dim3(B * 12), dim3(256), 0, s, h16, wqkv, bqkv, mask, ctx16, B);
-      else if (pk)
-        hipLaunchKernelGGL((bert_qkv_attn_kernel<0, 2, 1>), dim3(B * 6), dim3(512), 0, s, h16, wqkv, bqkv, mask, ctx16, B);
-      else if (opt().bert_qkv_attn_heads == 1)
-        hipLaunchKernelGGL((bert_qkv_attn_kernel<0, 1>), dim3(B * 12), dim3(256), 0, s, h16, wqkv, bqkv, mask, ctx16, B);
-      else
-        hipLaunchKernelGGL((bert_qkv_attn_kernel<0>), dim3(B * 6), dim3(512), 0, s, h16, wqkv, bqkv, mask, ctx16, B);
-      MEC_LAUNCH_CHECK();
+      MEC_TRY(launch_bert_qkv_attn(h16, w.wqkv, p.bqkv, tb.mask, ctx16, B, s, pk != nullptr));
       MEC_TRY(prof.end(TAG_BERT_ATTN, s));
     } else {
-      g.A = h16; g.B = wqkv; g.bias = bqkv; g.C16 = big16; g.M = M; g.N = 2304; g.K = BH;
+      g.A = h16; g.B = w.wqkv; g.bias = p.bqkv; g.C16 = big16; g.M = M; g.N = BQKV; g.K = BH;
       MEC_TRY(launch_gemm(g, s, &prof, TAG_BERT_QKV));
       MEC_TRY(prof.begin(TAG_BERT_ATTN, s));
-      if (pk)
-        hipLaunchKernelGGL(bert_attention_kernel<1>, dim3(B * BHEADS), dim3(256), 0, s, big16, mask, ctx16);
-      else
-        hipLaunchKernelGGL(bert_attention_kernel<0>, dim3(B * BHEADS), dim3(256), 0, s, big16, mask, ctx16);
-      MEC_LAUNCH_CHECK();
+      MEC_TRY(launch_bert_attention(big16, tb.mask, ctx16, B, s, pk != nullptr));
       MEC_TRY(prof.end(TAG_BERT_ATTN, s));
     }
-    const bool first = l == 0, last = l == BLAYERS - 1;
-    const float* pg2 = P + PRM_LAYER * (l - 1) + 8448;  // previous layer's LN2 (g2, b2)
-    // f32 stream ping-pong: O-proj reads h32 and writes t32, FFN2 reads t32 and writes h32,
-    // so no GEMM reads its own output (a launch stays idempotent: the tile autotuner
-    // re-runs candidates on the same buffers)
-    {
-      g = GemmParams();
-      g.A = ctx16; g.B = wo; g.bias = bo; g.R = h32; g.r_f32 = 1; g.C32 = t32; g.M = M; g.N = BH; g.K = BH;
-      if (!first) { g.r_stats = st2; g.r_g = pg2; g.r_b = pg2 + BH; }  // else: the embedding LN, written in full
-      MEC_TRY(launch_gemm(g, s, &prof, TAG_BERT_OPROJ));
-      MEC_TRY(prof.begin(TAG_BERT_LN, s));
-      launch_ln_rows(t32, M, g1, b1, nullptr, h16, st1, s, 0, 1.f);
-      MEC_LAUNCH_CHECK();
-      MEC_TRY(prof.end(TAG_BERT_LN, s));
-    }
-    g = GemmParams();
-    g.A = h16; g.B = wi; g.bias = bi; g.act = ACT_GELU; g.C16 = big16; g.M = M; g.N = BI; g.K = BH;
-    MEC_TRY(launch_gemm(g, s, &prof, TAG_BERT_FFN1));
-    g = GemmParams();
-    g.A = big16; g.B = wo2; g.bias = bo2; g.R = t32; g.r_f32 = 1; g.r_stats = st1; g.r_g = g1; g.r_b = b1;
-    g.C32 = h32; g.M = M; g.N = BH; g.K = BI;
-    MEC_TRY(launch_gemm(g, s, &prof, TAG_BERT_FFN2));
-    MEC_TRY(prof.begin(TAG_BERT_LN, s));
-    // the last LN's f32 output feeds the pooler / CLS feature, so it is written in full
-    // (in place: each wave holds its row in registers before writing it)
-    launch_ln_rows(h32, M, g2, b2, last ? h32 : nullptr, h16, st2, s, 0, 1.f);
-    MEC_LAUNCH_CHECK();
-    MEC_TRY(prof.end(TAG_BERT_LN, s));
+    MEC_TRY(tail(l, {M, h32, t32, ctx16, h16, big16, st1, st2, /*deferred_in=*/l != 0, /*full_out=*/last, /*tagged=*/true}));
   }
-  const float* head = P + PRM_LAYER * BLAYERS;
-  const float *WpT = head, *bp = WpT + (size_t)BH * BH, *WcT = bp + BH, *bc = WcT + (size_t)BH * 7;
-  // pooler: tanh(cls . Wp^T + bp) over the batch (also copies the CLS feature out)
-  bool compact = cls_last && BLAYERS > 1;
-  if (pk && !compact) {  // the samples' [CLS] rows of the final h32, in sample order
-    RowGather rg{};
-    rg.n = 1; rg.idx = cidx;
-    rg.src[0] = reinterpret_cast<const char*>(h32); rg.dst[0] = reinterpret_cast<char*>(h32c);
-    rg.sstride[0] = BH * 4; rg.bytes[0] = BH * 4;
-    MEC_TRY(launch_gather_rows(rg, NS, s));
-    compact = true;
-  }
-  MEC_TRY(launch_linear_mfma<BACT_TANH>(compact ? h32c : h32, compact ? (size_t)BH : (size_t)L * BH, NS, BH, WpT, bp,
-                                        BH, pooled, BH, cls, BH, s));
-  MEC_TRY(launch_head7(pooled, NS, BH, WcT, bc, logits, probs, s));
-  return 0;
+  return text_outputs(tb, P, h32, h32c, cls_last, pooled, cls, logits, probs, s);
 }
 
 }  // namespace mec

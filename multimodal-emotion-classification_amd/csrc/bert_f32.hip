@@ -11,16 +11,9 @@
 //   t32   = i32 . Wo2^T + bo2 + h32            gemm_f32
 //   h32   = LN(t32)
 // Head as on the f16 path (pooler tanh + classifier + softmax, block_ops.h).
-#include "block_ops.h"
-#include "models.h"
+#include "bert_model.h"
 
 namespace mec {
-
-namespace {
-constexpr int H = 768, FF = 3072, NH = 12, DH = 64, NL = 12, AL = 128;
-constexpr size_t PRM_LAYER = 2304 + 768 * 3 + 3072 + 768 * 3;
-constexpr size_t WT_LAYER = (size_t)2304 * 768 + 768 * 768 + 3072 * 768 + 768 * 3072;
-}  // namespace
 
 // K rows in LDS: 16 chunks of 16 B per 256-B row, chunk c stored at c ^ (row & 15), so the 16
 // rows of a ds_read_b128 lane group cover all 64 banks.
@@ -47,24 +40,24 @@ __global__ __launch_bounds__(256, 2) void bert_attention_f32_kernel(const float*
                                                                     float* __restrict__ ctx, f16* __restrict__ ctx16,
                                                                     long long lo, const float* __restrict__ qc,
                                                                     const int32_t* __restrict__ cidx) {
-  constexpr int LD = CLS ? 2 * H : 3 * H, KO = CLS ? 0 : H;
-  __shared__ __attribute__((aligned(16))) float sK[AL * DH];
-  __shared__ __attribute__((aligned(16))) float sV[AL * DH];
-  __shared__ float sBias[AL];
+  constexpr int LD = CLS ? 2 * BH : 3 * BH, KO = CLS ? 0 : BH;
+  __shared__ __attribute__((aligned(16))) float sK[ATT_L * BDH];
+  __shared__ __attribute__((aligned(16))) float sV[ATT_L * BDH];
+  __shared__ float sBias[ATT_L];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int b = blockIdx.x / NH, h = blockIdx.x - (blockIdx.x / NH) * NH;
+  const int b = blockIdx.x / BHEADS, h = blockIdx.x - (blockIdx.x / BHEADS) * BHEADS;
   const int cs = (CLS && PACK) ? cidx[b] : 0;
   const int bk = (CLS && PACK) ? cs >> 7 : b;  // the row whose K / V are staged
-  const float* base = qkv + (size_t)bk * AL * LD + h * DH;
+  const float* base = qkv + (size_t)bk * ATT_L * LD + h * BDH;
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     const int c = tid + 256 * i;
     const int row = c >> 4, kc = c & 15;
     const float* src = base + (size_t)row * LD + kc * 4;
     const float4 k = *reinterpret_cast<const float4*>(src + KO);
-    const float4 v = *reinterpret_cast<const float4*>(src + KO + H);
-    *reinterpret_cast<float4*>(sK + row * DH + kswz(row, kc) * 4) = k;
-    *reinterpret_cast<float4*>(sV + row * DH + kc * 4) = v;
+    const float4 v = *reinterpret_cast<const float4*>(src + KO + BH);
+    *reinterpret_cast<float4*>(sK + row * BDH + kswz(row, kc) * 4) = k;
+    *reinterpret_cast<float4*>(sV + row * BDH + kc * 4) = v;
   }
   stage_mask<PACK>(sBias, mask, bk, tid);
   const int lr = lane & 31, lh = lane >> 5;
@@ -72,7 +65,7 @@ __global__ __launch_bounds__(256, 2) void bert_attention_f32_kernel(const float*
   float4 qf[8];  // Q[q][8s + 4lh .. +3]
   if constexpr (CLS) {
     const bool own = wave == 0 && lr == 0;
-    const float* qrow = qc + (size_t)b * H + h * DH;
+    const float* qrow = qc + (size_t)b * BH + h * BDH;
 #pragma unroll
     for (int s = 0; s < 8; ++s)
       qf[s] = own ? *reinterpret_cast<const float4*>(qrow + (2 * s + lh) * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -92,7 +85,7 @@ __global__ __launch_bounds__(256, 2) void bert_attention_f32_kernel(const float*
     const int rk = 32 * t + lr;
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
-      const float4 kf = *reinterpret_cast<const float4*>(sK + rk * DH + kswz(rk, 2 * s + lh) * 4);
+      const float4 kf = *reinterpret_cast<const float4*>(sK + rk * BDH + kswz(rk, 2 * s + lh) * 4);
       st[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.x, qf[s].x, st[t], 0, 0, 0);
       st[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.y, qf[s].y, st[t], 0, 0, 0);
       st[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.z, qf[s].z, st[t], 0, 0, 0);
@@ -135,10 +128,10 @@ __global__ __launch_bounds__(256, 2) void bert_attention_f32_kernel(const float*
       const int key = 32 * t + (e & 3) + 8 * (e >> 2) + 4 * lh;
       const float p = st[t][e] * inv;
 #pragma unroll
-      for (int u = 0; u < 2; ++u) o[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(sV[key * DH + 32 * u + lr], p, o[u], 0, 0, 0);
+      for (int u = 0; u < 2; ++u) o[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(sV[key * BDH + 32 * u + lr], p, o[u], 0, 0, 0);
     }
   if (CLS && lr != 0) return;
-  const size_t obase = ((size_t)b * (CLS ? 1 : AL) + q) * H + h * DH;
+  const size_t obase = ((size_t)b * (CLS ? 1 : ATT_L) + q) * BH + h * BDH;
 #pragma unroll
   for (int u = 0; u < 2; ++u)
 #pragma unroll
@@ -160,124 +153,115 @@ __global__ __launch_bounds__(256, 2) void bert_attention_f32_kernel(const float*
     }
 }
 
+// kv: K | V of every token [rows * 128, 1536]; qc, ctx: the samples' [CLS] query / context rows [NS, 768];
+// cidx (or null): the packed form (mask = segment ids, sample b's [CLS] slot cidx[b])
+static int launch_bert_attention_f32_cls(const float* kv, const int32_t* mask, const float* qc, float* ctx, int NS,
+                                         hipStream_t s, const int32_t* cidx) {
+  if (cidx)
+    hipLaunchKernelGGL((bert_attention_f32_kernel<0, 1, 1>), dim3(NS * BHEADS), dim3(256), 0, s, kv, mask, ctx, nullptr,
+                       0LL, qc, cidx);
+  else
+    hipLaunchKernelGGL((bert_attention_f32_kernel<0, 1, 0>), dim3(NS * BHEADS), dim3(256), 0, s, kv, mask, ctx, nullptr,
+                       0LL, qc, nullptr);
+  MEC_LAUNCH_CHECK();
+  return 0;
+}
+
+// packed: mask holds the rows' uint8 segment ids and B counts packed rows
+static int launch_bert_attention_f32(const float* qkv, const int32_t* mask, float* ctx, int B, hipStream_t s,
+                                     bool packed) {
+  if (packed)
+    hipLaunchKernelGGL((bert_attention_f32_kernel<0, 0, 1>), dim3(B * BHEADS), dim3(256), 0, s, qkv, mask, ctx, nullptr,
+                       0LL, nullptr, nullptr);
+  else
+    hipLaunchKernelGGL((bert_attention_f32_kernel<0, 0, 0>), dim3(B * BHEADS), dim3(256), 0, s, qkv, mask, ctx, nullptr,
+                       0LL, nullptr, nullptr);
+  MEC_LAUNCH_CHECK();
+  return 0;
+}
+
+namespace {
+// The fp32 forward's form of TailRows (bert_model.h): no f16 operands, no deferred LayerNorm
+struct TailRowsF32 {
+  int n;
+  float *h32, *t32;  // the stream pair: both GEMMs add h32 into t32, both LayerNorms write t32 -> h32
+  float *ctx, *ffn;  // the context (in), the FFN intermediate
+  bool tagged;
+};
+}  // namespace
+
 int TextModel::forward_f32(const int32_t* ids, const int32_t* mask, int B, int L, float* cls, float* logits,
                            float* probs, hipStream_t s, const TextPack* pk) {
   MEC_REQUIRE(wts32.p, "text: fp32 weights missing (handle created at f16 precision)");
-  const int M = B * L;
-  const int NS = pk ? pk->ns : B;  // samples (TextModel::forward): rows of the compact buffers and the outputs
-  // workspace: h32 | t32 | ctx32 (f32 [M,768]) ; big32 f32 [M,3072] (qkv [M,2304], then FFN) ; pooled [B,768] ;
-  // the [CLS]-row buffers of the last layer (bert_cls_last): h32c | t32c | qc | ctxc [B,768], fc [B,3072]
+  // workspace: h32 | t32 | ctx32 (f32 [M,768]) ; big32 f32 [M,3072] (qkv [M,2304], then FFN) ; pooled [NS,768] ;
+  // the [CLS]-row buffers of the last layer (bert_cls_last): h32c | t32c | qc | ctxc [NS,768], fc [NS,3072]
   float *h32, *t32, *ctx32, *big32, *pooled, *h32c, *t32c, *qc, *ctxc, *fc;
-  PackBufs pkb;
-  MEC_TRY(carve(ws, [&](Carver& c) {
-    h32 = c.take<float>((size_t)M * H);
-    t32 = c.take<float>((size_t)M * H);
-    ctx32 = c.take<float>((size_t)M * H);
-    big32 = c.take<float>((size_t)M * FF);
-    pooled = c.take<float>((size_t)NS * H);
-    h32c = c.take<float>((size_t)NS * H);
-    t32c = c.take<float>((size_t)NS * H);
-    qc = c.take<float>((size_t)NS * H);
-    ctxc = c.take<float>((size_t)NS * H);
-    fc = c.take<float>((size_t)NS * FF);
-    if (pk) pkb.take(c, M, NS);
+  TextBatch tb;
+  MEC_TRY(text_prologue(tb, ws, ids, mask, B, pk, s, [&](Carver& c) {
+    const size_t M = tb.M, NS = tb.NS;
+    h32 = c.take<float>(M * BH);
+    t32 = c.take<float>(M * BH);
+    ctx32 = c.take<float>(M * BH);
+    big32 = c.take<float>(M * BI);
+    pooled = c.take<float>(NS * BH);
+    h32c = c.take<float>(NS * BH);
+    t32c = c.take<float>(NS * BH);
+    qc = c.take<float>(NS * BH);
+    ctxc = c.take<float>(NS * BH);
+    fc = c.take<float>(NS * BI);
   }));
+  const int M = tb.M, NS = tb.NS;
   const bool cls_last = opt().bert_cls_last != 0;
-  const int32_t* posid = nullptr;
-  const int32_t* cidx = nullptr;
-  if (pk) {
-    MEC_TRY(launch_bert_pack(ids, *pk, B, pkb.ids, pkb.pos, pkb.seg, pkb.cidx, s));
-    ids = pkb.ids; posid = pkb.pos; cidx = pkb.cidx;
-    mask = reinterpret_cast<const int32_t*>(pkb.seg);
-  }
-  const long long gs = pk ? 1 : AL;  // rows between gathered [CLS] rows: cidx counts slots
-
-  MEC_TRY(launch_bert_embed_ln(ids, M, L, emb.as<float>(), h32, nullptr, s, 0, 1.f, posid));
   const float* W = wts32.as<float>();
   const float* P = prm.as<float>();
-  for (int l = 0; l < NL; ++l) {
-    const float* wqkv = W + WT_LAYER * l;
-    const float* wo = wqkv + (size_t)2304 * H;
-    const float* wi = wo + (size_t)H * H;
-    const float* wo2 = wi + (size_t)FF * H;
-    const float* pl = P + PRM_LAYER * l;
-    const float *bqkv = pl, *bo = pl + 2304, *g1 = pl + 3072, *b1 = pl + 3840, *bi = pl + 4608, *bo2 = pl + 7680,
-                *g2 = pl + 8448, *b2 = pl + 9216;
+
+  auto tail = [&](int l, const TailRowsF32& r) -> int {
+    const LayerWeights<const float> w = layer_weights(W, l);
+    const LayerParams<const float> p = layer_params(P, l);
+    auto tag = [&](int t) { return r.tagged ? t : (int)TAG_NONE; };
     GemmParams g;
-    if (cls_last && l == NL - 1) {
+    g.A = r.ctx; g.B32 = w.wo; g.bias = p.bo; g.R = r.h32; g.r_f32 = 1; g.C32 = r.t32; g.M = r.n; g.N = BH; g.K = BH;
+    MEC_TRY(launch_gemm_f32(g, s, &prof, tag(TAG_BERT_OPROJ)));
+    MEC_TRY(prof.begin(tag(TAG_BERT_LN), s));
+    MEC_TRY(launch_bert_layernorm(r.t32, r.n, p.g1, p.b1, r.h32, nullptr, nullptr, s));
+    MEC_TRY(prof.end(tag(TAG_BERT_LN), s));
+    g = GemmParams();
+    g.A = r.h32; g.B32 = w.wi; g.bias = p.bi; g.act = ACT_GELU_EXACT; g.C32 = r.ffn; g.M = r.n; g.N = BI; g.K = BH;
+    MEC_TRY(launch_gemm_f32(g, s, &prof, tag(TAG_BERT_FFN1)));
+    g = GemmParams();
+    g.A = r.ffn; g.B32 = w.wo2; g.bias = p.bo2; g.R = r.h32; g.r_f32 = 1; g.C32 = r.t32; g.M = r.n; g.N = BH; g.K = BI;
+    MEC_TRY(launch_gemm_f32(g, s, &prof, tag(TAG_BERT_FFN2)));
+    MEC_TRY(prof.begin(tag(TAG_BERT_LN), s));
+    MEC_TRY(launch_bert_layernorm(r.t32, r.n, p.g2, p.b2, r.h32, nullptr, nullptr, s));
+    MEC_TRY(prof.end(tag(TAG_BERT_LN), s));
+    return 0;
+  };
+
+  MEC_TRY(launch_bert_embed_ln(tb.ids, M, L, emb.as<float>(), h32, nullptr, s, 0, 1.f, tb.posid));
+  for (int l = 0; l < BLAYERS; ++l) {
+    const LayerWeights<const float> w = layer_weights(W, l);
+    const LayerParams<const float> p = layer_params(P, l);
+    GemmParams g;
+    if (cls_last && l == BLAYERS - 1) {
       // [CLS]-only last layer (TextModel::forward): K / V for every token, the rest on the [CLS] rows
-      RowGather rg{};
-      rg.n = 1; rg.idx = cidx;
-      rg.src[0] = reinterpret_cast<const char*>(h32); rg.dst[0] = reinterpret_cast<char*>(h32c);
-      rg.sstride[0] = gs * H * 4; rg.bytes[0] = H * 4;
-      MEC_TRY(launch_gather_rows(rg, NS, s));
-      g.A = h32; g.B32 = wqkv + (size_t)H * H; g.bias = bqkv + H; g.C32 = big32; g.M = M; g.N = 2 * H; g.K = H;
+      MEC_TRY(gather_cls_rows(tb, {{h32, h32c, BH * 4}}, s));
+      g.A = h32; g.B32 = w.wqkv + (size_t)BH * BH; g.bias = p.bqkv + BH; g.C32 = big32; g.M = M; g.N = 2 * BH; g.K = BH;
       MEC_TRY(launch_gemm_f32(g, s, &prof, TAG_NONE));  // K | V [M, 1536]
       g = GemmParams();
-      g.A = h32c; g.B32 = wqkv; g.bias = bqkv; g.C32 = qc; g.M = NS; g.N = H; g.K = H;
+      g.A = h32c; g.B32 = w.wqkv; g.bias = p.bqkv; g.C32 = qc; g.M = NS; g.N = BH; g.K = BH;
       MEC_TRY(launch_gemm_f32(g, s, &prof, TAG_NONE));  // Q of the [CLS] rows
-      if (pk)
-        hipLaunchKernelGGL((bert_attention_f32_kernel<0, 1, 1>), dim3(NS * NH), dim3(256), 0, s, big32, mask, ctxc,
-                           nullptr, 0LL, qc, cidx);
-      else
-        hipLaunchKernelGGL((bert_attention_f32_kernel<0, 1, 0>), dim3(B * NH), dim3(256), 0, s, big32, mask, ctxc,
-                           nullptr, 0LL, qc, nullptr);
-      MEC_LAUNCH_CHECK();
-      g = GemmParams();
-      g.A = ctxc; g.B32 = wo; g.bias = bo; g.R = h32c; g.r_f32 = 1; g.C32 = t32c; g.M = NS; g.N = H; g.K = H;
-      MEC_TRY(launch_gemm_f32(g, s, &prof, TAG_NONE));
-      MEC_TRY(launch_bert_layernorm(t32c, NS, g1, b1, h32c, nullptr, nullptr, s));
-      g = GemmParams();
-      g.A = h32c; g.B32 = wi; g.bias = bi; g.act = ACT_GELU_EXACT; g.C32 = fc; g.M = NS; g.N = FF; g.K = H;
-      MEC_TRY(launch_gemm_f32(g, s, &prof, TAG_NONE));
-      g = GemmParams();
-      g.A = fc; g.B32 = wo2; g.bias = bo2; g.R = h32c; g.r_f32 = 1; g.C32 = t32c; g.M = NS; g.N = H; g.K = FF;
-      MEC_TRY(launch_gemm_f32(g, s, &prof, TAG_NONE));
-      MEC_TRY(launch_bert_layernorm(t32c, NS, g2, b2, h32c, nullptr, nullptr, s));
+      MEC_TRY(launch_bert_attention_f32_cls(big32, tb.mask, qc, ctxc, NS, s, tb.cidx));
+      MEC_TRY(tail(l, {NS, h32c, t32c, ctxc, fc, /*tagged=*/false}));
       break;
     }
-    g.A = h32; g.B32 = wqkv; g.bias = bqkv; g.C32 = big32; g.M = M; g.N = 2304; g.K = H;
+    g.A = h32; g.B32 = w.wqkv; g.bias = p.bqkv; g.C32 = big32; g.M = M; g.N = BQKV; g.K = BH;
     MEC_TRY(launch_gemm_f32(g, s, &prof, TAG_BERT_QKV));
     MEC_TRY(prof.begin(TAG_BERT_ATTN, s));
-    if (pk)
-      hipLaunchKernelGGL((bert_attention_f32_kernel<0, 0, 1>), dim3(B * NH), dim3(256), 0, s, big32, mask, ctx32, nullptr,
-                         0LL, nullptr, nullptr);
-    else
-      hipLaunchKernelGGL((bert_attention_f32_kernel<0, 0, 0>), dim3(B * NH), dim3(256), 0, s, big32, mask, ctx32, nullptr,
-                         0LL, nullptr, nullptr);
-    MEC_LAUNCH_CHECK();
+    MEC_TRY(launch_bert_attention_f32(big32, tb.mask, ctx32, B, s, pk != nullptr));
     MEC_TRY(prof.end(TAG_BERT_ATTN, s));
-    g = GemmParams();
-    g.A = ctx32; g.B32 = wo; g.bias = bo; g.R = h32; g.r_f32 = 1; g.C32 = t32; g.M = M; g.N = H; g.K = H;
-    MEC_TRY(launch_gemm_f32(g, s, &prof, TAG_BERT_OPROJ));
-    MEC_TRY(prof.begin(TAG_BERT_LN, s));
-    MEC_TRY(launch_bert_layernorm(t32, M, g1, b1, h32, nullptr, nullptr, s));
-    MEC_TRY(prof.end(TAG_BERT_LN, s));
-    g = GemmParams();
-    g.A = h32; g.B32 = wi; g.bias = bi; g.act = ACT_GELU_EXACT; g.C32 = big32; g.M = M; g.N = FF; g.K = H;
-    MEC_TRY(launch_gemm_f32(g, s, &prof, TAG_BERT_FFN1));
-    g = GemmParams();
-    g.A = big32; g.B32 = wo2; g.bias = bo2; g.R = h32; g.r_f32 = 1; g.C32 = t32; g.M = M; g.N = H; g.K = FF;
-    MEC_TRY(launch_gemm_f32(g, s, &prof, TAG_BERT_FFN2));
-    MEC_TRY(prof.begin(TAG_BERT_LN, s));
-    MEC_TRY(launch_bert_layernorm(t32, M, g2, b2, h32, nullptr, nullptr, s));
-    MEC_TRY(prof.end(TAG_BERT_LN, s));
+    MEC_TRY(tail(l, {M, h32, t32, ctx32, big32, /*tagged=*/true}));
   }
-  const float* head = P + PRM_LAYER * NL;
-  const float *WpT = head, *bp = WpT + (size_t)H * H, *WcT = bp + H, *bc = WcT + (size_t)H * 7;
-  bool compact = cls_last;
-  if (pk && !compact) {  // the samples' [CLS] rows of the final h32, in sample order
-    RowGather rg{};
-    rg.n = 1; rg.idx = cidx;
-    rg.src[0] = reinterpret_cast<const char*>(h32); rg.dst[0] = reinterpret_cast<char*>(h32c);
-    rg.sstride[0] = H * 4; rg.bytes[0] = H * 4;
-    MEC_TRY(launch_gather_rows(rg, NS, s));
-    compact = true;
-  }
-  MEC_TRY(launch_linear_mfma<BACT_TANH>(compact ? h32c : h32, compact ? (size_t)H : (size_t)L * H, NS, H, WpT, bp,
-                                        H, pooled, H, cls, H, s));
-  MEC_TRY(launch_head7(pooled, NS, H, WcT, bc, logits, probs, s));
-  return 0;
+  return text_outputs(tb, P, h32, h32c, cls_last, pooled, cls, logits, probs, s);
 }
 
 // fp32x3 path: the fp32 path's structure with every GEMM on split-f16 operands (gemm_glds.hip
@@ -292,172 +276,125 @@ int TextModel::forward_f32(const int32_t* ids, const int32_t* mask, int B, int L
 //   h hi/lo, st2 = LN(h32)
 int TextModel::forward_x3(const int32_t* ids, const int32_t* mask, int B, int L, float* cls, float* logits,
                           float* probs, hipStream_t s, const TextPack* pk) {
-  MEC_REQUIRE(wts.p && x3_lo && x3_scale.size() == 4 * NL, "text: fp32x3 weights missing");
-  const int M = B * L;
-  const int NS = pk ? pk->ns : B;  // samples (TextModel::forward): rows of the compact buffers and the outputs
-  const long long MH = (long long)M * H, MF = (long long)M * FF;
+  MEC_REQUIRE(wts.p && x3_lo && x3_layers.size() == (size_t)BLAYERS, "text: fp32x3 weights missing");
   // workspace: h32 | t32 (f32 [M,768]) ; h hi|lo, ctx hi|lo (f16 2x[M,768]) ; big: qkv hi|lo
-  // (f16 2x[M,2304]), then the FFN intermediate hi|lo (f16 2x[M,3072]) ; pooled [B,768]
-  // + the [CLS]-row buffers of the last layer (bert_cls_last): h32c | t32c (f32 [B,768]) ; hsc | qsc | csc
-  // (f16 planes 2x[B,768]) ; fsc (f16 planes 2x[B,3072])
-  const long long BHc = (long long)NS * H, BFc = (long long)NS * FF;
-  // + the LayerNorm row stats st1 | st2 ([M] float2; deferred LayerNorm, below) and st2c ([B] float2)
+  // (f16 2x[M,2304]), then the FFN intermediate hi|lo (f16 2x[M,3072]) ; pooled [NS,768]
+  // + the [CLS]-row buffers of the last layer (bert_cls_last): h32c | t32c (f32 [NS,768]) ; hsc | qsc | csc
+  // (f16 planes 2x[NS,768]) ; fsc (f16 planes 2x[NS,3072])
+  // + the LayerNorm row stats st1 | st2 ([M] float2 each; deferred LayerNorm, below) and st1c | st2c ([NS])
   float *h32, *t32, *pooled, *h32c, *t32c;
   f16 *hs, *cs, *bigs, *hsc, *qsc, *csc, *fsc;
-  float2 *st1, *st2c;
-  PackBufs pkb;
-  MEC_TRY(carve(ws, [&](Carver& c) {
-    h32 = c.take<float>((size_t)MH);
-    t32 = c.take<float>((size_t)MH);
-    hs = c.take<f16>((size_t)MH * 2);
-    cs = c.take<f16>((size_t)MH * 2);
-    bigs = c.take<f16>((size_t)MF * 2);
-    pooled = c.take<float>((size_t)NS * H);
-    h32c = c.take<float>((size_t)BHc);
-    t32c = c.take<float>((size_t)BHc);
-    hsc = c.take<f16>((size_t)BHc * 2);
-    qsc = c.take<f16>((size_t)BHc * 2);
-    csc = c.take<f16>((size_t)BHc * 2);
-    fsc = c.take<f16>((size_t)BFc * 2);
-    st1 = c.take<float2>((size_t)M * 2);  // LN1 | LN2 row stats [M] each
-    st2c = c.take<float2>((size_t)NS);    // LN2 row stats of the [CLS] rows
-    if (pk) pkb.take(c, M, NS);
+  float2 *st1, *st1c;
+  TextBatch tb;
+  MEC_TRY(text_prologue(tb, ws, ids, mask, B, pk, s, [&](Carver& c) {
+    const size_t M = tb.M, NS = tb.NS;
+    h32 = c.take<float>(M * BH);
+    t32 = c.take<float>(M * BH);
+    hs = c.take<f16>(M * BH * 2);
+    cs = c.take<f16>(M * BH * 2);
+    bigs = c.take<f16>(M * BI * 2);
+    pooled = c.take<float>(NS * BH);
+    h32c = c.take<float>(NS * BH);
+    t32c = c.take<float>(NS * BH);
+    hsc = c.take<f16>(NS * BH * 2);
+    qsc = c.take<f16>(NS * BH * 2);
+    csc = c.take<f16>(NS * BH * 2);
+    fsc = c.take<f16>(NS * BI * 2);
+    st1 = c.take<float2>(M * 2);
+    st1c = c.take<float2>(NS * 2);
   }));
+  const int M = tb.M, NS = tb.NS;
+  const long long MH = (long long)M * BH, NSH = (long long)NS * BH;  // lo-plane offsets of [M,768] / [NS,768] planes
   float2* st2 = st1 + M;
+  float2* st2c = st1c + NS;
   const bool cls_last = opt().bert_cls_last != 0;
   const int gelu_act = opt().gelu_x3 ? ACT_GELU_F32 : ACT_GELU_EXACT;  // FFN1's erf GELU
-  const int32_t* posid = nullptr;
-  const int32_t* cidx = nullptr;
-  if (pk) {
-    MEC_TRY(launch_bert_pack(ids, *pk, B, pkb.ids, pkb.pos, pkb.seg, pkb.cidx, s));
-    ids = pkb.ids; posid = pkb.pos; cidx = pkb.cidx;
-    mask = reinterpret_cast<const int32_t*>(pkb.seg);
-  }
-  const long long gs = pk ? 1 : AL;  // rows between gathered [CLS] rows: cidx counts slots
-
-  MEC_TRY(launch_bert_embed_ln(ids, M, L, emb.as<float>(), h32, hs, s, MH, std::ldexp(1.0f, x3_s_emb), posid));
   const f16* W = wts.as<f16>();
   const float* P = prm.as<float>();
   const long long wlo = (long long)x3_lo;
-  for (int l = 0; l < NL; ++l) {
-    const f16* wqkv = W + WT_LAYER * l;
-    const f16* wo = wqkv + (size_t)2304 * H;
-    const f16* wi = wo + (size_t)H * H;
-    const f16* wo2 = wi + (size_t)FF * H;
-    const float* sc = x3_scale.data() + 4 * l;
-    const float* pl = P + PRM_LAYER * l;
-    const float *bo = pl + 2304, *g1 = pl + 3072, *b1 = pl + 3840, *bi = pl + 4608, *bo2 = pl + 7680,
-                *g2 = pl + 8448, *b2 = pl + 9216;
-    // activation-plane scales (TextModel::create): Q / K / V through the pre-scaled Wqkv planes and bqkv
-    // (x3b), the scores by 1/8 2^-(s_q + s_k), the LN outputs by up1 / up2, the FFN intermediate by
-    // cscale (ffs)
-    const float* bqkv = x3b.as<float>() + (size_t)2304 * l;
-    const float qks = std::ldexp(0.125f, -(x3_s_q[l] + x3_s_k[l]));
-    const float up1 = std::ldexp(1.0f, x3_s_ln1[l]), up2 = std::ldexp(1.0f, x3_s_ln2[l]);
-    const float ffs = std::ldexp(1.0f, x3_s_ffn[l]);
+
+  // Deferred LayerNorm (as on the f16 path): the LN kernels write the GEMM operand planes and the row
+  // (mean, rstd) only; the f32 LN output is needed only as the next residual, which the O-proj / FFN2
+  // epilogue re-derives from the pre-LN sum with the LN kernel's own expression (GemmParams::r_stats):
+  // same bits, two 100-MB f32 writes per layer fewer at B = 256. The f32 stream ping-pongs, so no GEMM
+  // reads its own output. Plane scales (TextModel::create): LN outputs 2^s_ln1 / 2^s_ln2, FFN intermediate
+  // cscale 2^s_ffn; each GEMM's oscale undoes its operands' (X3Layer::scale).
+  auto tail = [&](int l, const TailRows& r) -> int {
+    const LayerWeights<const f16> w = layer_weights(W, l);
+    const LayerParams<const float> p = layer_params(P, l);
+    const X3Layer& x = x3_layers[l];
+    const long long nh = (long long)r.n * BH, nf = (long long)r.n * BI;
+    auto tag = [&](int t) { return r.tagged ? t : (int)TAG_NONE; };
     GemmParams g;
-    if (cls_last && l == NL - 1) {
+    g.split = 1; g.A = r.ctx; g.a_lo = nh; g.B = w.wo; g.b_lo = wlo; g.oscale = x.scale[1];
+    g.bias = p.bo; g.R = r.h32; g.r_f32 = 1; g.C32 = r.t32; g.M = r.n; g.N = BH; g.K = BH;
+    if (r.deferred_in) { g.r_stats = r.st2; g.r_g = layer_params(P, l - 1).g2; g.r_b = layer_params(P, l - 1).b2; }
+    MEC_TRY(launch_gemm(g, s, &prof, tag(TAG_BERT_OPROJ)));
+    MEC_TRY(prof.begin(tag(TAG_BERT_LN), s));
+    MEC_TRY(launch_bert_layernorm(r.t32, r.n, p.g1, p.b1, nullptr, r.op, r.st1, s, nh, std::ldexp(1.0f, x.s_ln1)));
+    MEC_TRY(prof.end(tag(TAG_BERT_LN), s));
+    g = GemmParams();
+    g.split = 1; g.A = r.op; g.a_lo = nh; g.B = w.wi; g.b_lo = wlo; g.oscale = x.scale[2];
+    g.bias = p.bi; g.act = gelu_act; g.C16 = r.ffn; g.c_lo = nf; g.cscale = std::ldexp(1.0f, x.s_ffn);
+    g.M = r.n; g.N = BI; g.K = BH;
+    MEC_TRY(launch_gemm(g, s, &prof, tag(TAG_BERT_FFN1)));
+    g = GemmParams();
+    g.split = 1; g.A = r.ffn; g.a_lo = nf; g.B = w.wo2; g.b_lo = wlo; g.oscale = x.scale[3];
+    g.bias = p.bo2; g.R = r.t32; g.r_f32 = 1; g.r_stats = r.st1; g.r_g = p.g1; g.r_b = p.b1; g.C32 = r.h32;
+    g.M = r.n; g.N = BH; g.K = BI;
+    MEC_TRY(launch_gemm(g, s, &prof, tag(TAG_BERT_FFN2)));
+    MEC_TRY(prof.begin(tag(TAG_BERT_LN), s));
+    MEC_TRY(launch_bert_layernorm(r.h32, r.n, p.g2, p.b2, r.full_out ? r.h32 : nullptr, r.op, r.st2, s, nh,
+                                  std::ldexp(1.0f, x.s_ln2)));
+    MEC_TRY(prof.end(tag(TAG_BERT_LN), s));
+    return 0;
+  };
+
+  MEC_TRY(launch_bert_embed_ln(tb.ids, M, L, emb.as<float>(), h32, hs, s, MH, std::ldexp(1.0f, x3_s_emb), tb.posid));
+  for (int l = 0; l < BLAYERS; ++l) {
+    const LayerWeights<const f16> w = layer_weights(W, l);
+    const X3Layer& x = x3_layers[l];
+    // Q / K / V planes carry 2^s_q | 2^s_k | 2^s_v through the pre-scaled Wqkv planes and bqkv (x3b); the
+    // scores are scaled back by qks = 1/8 2^-(s_q + s_k)
+    const float* bqkv = x3b.as<float>() + (size_t)BQKV * l;
+    const float qks = std::ldexp(0.125f, -(x.s_q + x.s_k));
+    const bool last = l == BLAYERS - 1;
+    GemmParams g;
+    if (cls_last && last) {
       // [CLS]-only last layer (TextModel::forward): K / V for every token, the rest on the [CLS] rows
-      RowGather rg{};
-      rg.n = 3; rg.idx = cidx;
-      rg.src[0] = reinterpret_cast<const char*>(h32); rg.dst[0] = reinterpret_cast<char*>(h32c);
-      rg.sstride[0] = gs * H * 4; rg.bytes[0] = H * 4;
-      rg.src[1] = reinterpret_cast<const char*>(hs); rg.dst[1] = reinterpret_cast<char*>(hsc);
-      rg.sstride[1] = gs * H * 2; rg.bytes[1] = H * 2;
-      rg.src[2] = reinterpret_cast<const char*>(hs + MH); rg.dst[2] = reinterpret_cast<char*>(hsc + BHc);
-      rg.sstride[2] = gs * H * 2; rg.bytes[2] = H * 2;
-      if (l > 0) {  // h32 holds layer l-1's pre-LN2 sum (deferred LayerNorm): its stats too
-        rg.n = 4;
-        rg.src[3] = reinterpret_cast<const char*>(st2); rg.dst[3] = reinterpret_cast<char*>(st2c);
-        rg.sstride[3] = gs * 8; rg.bytes[3] = 8;
-      }
-      MEC_TRY(launch_gather_rows(rg, NS, s));
-      const float* pg2 = P + PRM_LAYER * (l - 1) + 8448;  // layer l-1's LN2 (g2, b2)
-      const long long kvlo = (long long)M * 2 * H;
-      g.split = 1; g.A = hs; g.a_lo = MH; g.B = wqkv + (size_t)H * H; g.b_lo = wlo; g.oscale = sc[0];
-      g.bias = bqkv + H; g.C16 = bigs; g.c_lo = kvlo; g.M = M; g.N = 2 * H; g.K = H;
+      MEC_TRY(gather_cls_rows(
+          tb, {{h32, h32c, BH * 4}, {hs, hsc, BH * 2}, {hs + MH, hsc + NSH, BH * 2}, {st2, st2c, 8}}, s));
+      const long long kvlo = (long long)M * 2 * BH;
+      g.split = 1; g.A = hs; g.a_lo = MH; g.B = w.wqkv + (size_t)BH * BH; g.b_lo = wlo; g.oscale = x.scale[0];
+      g.bias = bqkv + BH; g.C16 = bigs; g.c_lo = kvlo; g.M = M; g.N = 2 * BH; g.K = BH;
       MEC_TRY(launch_gemm(g, s, &prof, TAG_NONE));  // K | V planes [M, 1536]
       g = GemmParams();
-      g.split = 1; g.A = hsc; g.a_lo = BHc; g.B = wqkv; g.b_lo = wlo; g.oscale = sc[0];
-      g.bias = bqkv; g.C16 = qsc; g.c_lo = BHc; g.M = NS; g.N = H; g.K = H;
+      g.split = 1; g.A = hsc; g.a_lo = NSH; g.B = w.wqkv; g.b_lo = wlo; g.oscale = x.scale[0];
+      g.bias = bqkv; g.C16 = qsc; g.c_lo = NSH; g.M = NS; g.N = BH; g.K = BH;
       MEC_TRY(launch_gemm(g, s, &prof, TAG_NONE));  // Q planes of the [CLS] rows
-      MEC_TRY(launch_bert_attention_x3_cls(bigs, kvlo, mask, qsc, BHc, csc, BHc, NS, qks, s, cidx));
-      g = GemmParams();
-      g.split = 1; g.A = csc; g.a_lo = BHc; g.B = wo; g.b_lo = wlo; g.oscale = sc[1];
-      g.bias = bo; g.R = h32c; g.r_f32 = 1; g.C32 = t32c; g.M = NS; g.N = H; g.K = H;
-      if (l > 0) { g.r_stats = st2c; g.r_g = pg2; g.r_b = pg2 + H; }
-      MEC_TRY(launch_gemm(g, s, &prof, TAG_NONE));
-      MEC_TRY(launch_bert_layernorm(t32c, NS, g1, b1, h32c, hsc, nullptr, s, BHc, up1));
-      g = GemmParams();
-      g.split = 1; g.A = hsc; g.a_lo = BHc; g.B = wi; g.b_lo = wlo; g.oscale = sc[2];
-      g.bias = bi; g.act = gelu_act; g.C16 = fsc; g.c_lo = BFc; g.cscale = ffs; g.M = NS; g.N = FF; g.K = H;
-      MEC_TRY(launch_gemm(g, s, &prof, TAG_NONE));
-      g = GemmParams();
-      g.split = 1; g.A = fsc; g.a_lo = BFc; g.B = wo2; g.b_lo = wlo; g.oscale = sc[3];
-      g.bias = bo2; g.R = h32c; g.r_f32 = 1; g.C32 = t32c; g.M = NS; g.N = H; g.K = FF;
-      MEC_TRY(launch_gemm(g, s, &prof, TAG_NONE));
-      MEC_TRY(launch_bert_layernorm(t32c, NS, g2, b2, h32c, hsc, nullptr, s, BHc, up2));
+      MEC_TRY(launch_bert_attention_x3_cls(bigs, kvlo, tb.mask, qsc, NSH, csc, NSH, NS, qks, s, tb.cidx));
+      MEC_TRY(tail(l, {NS, h32c, t32c, csc, hsc, fsc, st1c, st2c, /*deferred_in=*/true, /*full_out=*/true, /*tagged=*/false}));
       break;
     }
     // QKV projection + attention fused (Q / K / V stay on chip). The fused kernel sums in the K-interleaved
     // term order only, so with gemm_x3_order 0 (pass-major) the split GEMM + attention pair runs instead
     // and every split product of the forward keeps one term order
-    if (opt().bert_qkv_attn == 1 && L == 128 && opt().gemm_x3_order == 1) {
+    if (opt().bert_qkv_attn == 1 && L == ATT_L && opt().gemm_x3_order == 1) {
       MEC_TRY(prof.begin(TAG_BERT_QKV, s));
-      MEC_TRY(launch_bert_qkv_attn_x3(hs, MH, wqkv, wlo, sc[0], bqkv, mask, cs, MH, B, qks, s, pk != nullptr));
+      MEC_TRY(launch_bert_qkv_attn_x3(hs, MH, w.wqkv, wlo, x.scale[0], bqkv, tb.mask, cs, MH, B, qks, s, pk != nullptr));
       MEC_TRY(prof.end(TAG_BERT_QKV, s));
     } else {
-      g.split = 1; g.A = hs; g.a_lo = MH; g.B = wqkv; g.b_lo = wlo; g.oscale = sc[0];
-      g.bias = bqkv; g.C16 = bigs; g.c_lo = (long long)M * 2304; g.M = M; g.N = 2304; g.K = H;
+      const long long qlo = (long long)M * BQKV;
+      g.split = 1; g.A = hs; g.a_lo = MH; g.B = w.wqkv; g.b_lo = wlo; g.oscale = x.scale[0];
+      g.bias = bqkv; g.C16 = bigs; g.c_lo = qlo; g.M = M; g.N = BQKV; g.K = BH;
       MEC_TRY(launch_gemm(g, s, &prof, TAG_BERT_QKV));
       MEC_TRY(prof.begin(TAG_BERT_ATTN, s));
-      MEC_TRY(launch_bert_attention_x3(bigs, (long long)M * 2304, mask, cs, MH, B, qks, s, pk != nullptr));
+      MEC_TRY(launch_bert_attention_x3(bigs, qlo, tb.mask, cs, MH, B, qks, s, pk != nullptr));
       MEC_TRY(prof.end(TAG_BERT_ATTN, s));
     }
-    // deferred LayerNorm (as on the f16 path): the LN kernels write the GEMM operand planes and the
-    // row (mean, rstd) only; the f32 LN output is needed only as the next residual, which the
-    // O-proj / FFN2 epilogue re-derives from the pre-LN sum with the LN kernel's own expression
-    // (GemmParams::r_stats): same bits, two 100-MB f32 writes per layer fewer at B = 256. The f32
-    // stream ping-pongs (O-proj h32 -> t32, FFN2 t32 -> h32) so no GEMM reads its own output.
-    const bool first = l == 0, last = l == NL - 1;
-    const float* pg2 = P + PRM_LAYER * (l - 1) + 8448;  // layer l-1's LN2 (g2, b2)
-    g = GemmParams();
-    g.split = 1; g.A = cs; g.a_lo = MH; g.B = wo; g.b_lo = wlo; g.oscale = sc[1];
-    g.bias = bo; g.R = h32; g.r_f32 = 1; g.C32 = t32; g.M = M; g.N = H; g.K = H;
-    if (!first) { g.r_stats = st2; g.r_g = pg2; g.r_b = pg2 + H; }  // else: the embedding LN, written in full
-    MEC_TRY(launch_gemm(g, s, &prof, TAG_BERT_OPROJ));
-    MEC_TRY(prof.begin(TAG_BERT_LN, s));
-    MEC_TRY(launch_bert_layernorm(t32, M, g1, b1, nullptr, hs, st1, s, MH, up1));
-    MEC_TRY(prof.end(TAG_BERT_LN, s));
-    g = GemmParams();
-    g.split = 1; g.A = hs; g.a_lo = MH; g.B = wi; g.b_lo = wlo; g.oscale = sc[2];
-    g.bias = bi; g.act = gelu_act; g.C16 = bigs; g.c_lo = MF; g.cscale = ffs; g.M = M; g.N = FF; g.K = H;
-    MEC_TRY(launch_gemm(g, s, &prof, TAG_BERT_FFN1));
-    g = GemmParams();
-    g.split = 1; g.A = bigs; g.a_lo = MF; g.B = wo2; g.b_lo = wlo; g.oscale = sc[3];
-    g.bias = bo2; g.R = t32; g.r_f32 = 1; g.r_stats = st1; g.r_g = g1; g.r_b = b1; g.C32 = h32;
-    g.M = M; g.N = H; g.K = FF;
-    MEC_TRY(launch_gemm(g, s, &prof, TAG_BERT_FFN2));
-    MEC_TRY(prof.begin(TAG_BERT_LN, s));
-    // the last LN's f32 output feeds the pooler, so it is written in full (in place)
-    MEC_TRY(launch_bert_layernorm(h32, M, g2, b2, last ? h32 : nullptr, hs, st2, s, MH, up2));
-    MEC_TRY(prof.end(TAG_BERT_LN, s));
+    MEC_TRY(tail(l, {M, h32, t32, cs, hs, bigs, st1, st2, /*deferred_in=*/l != 0, /*full_out=*/last, /*tagged=*/true}));
   }
-  const float* head = P + PRM_LAYER * NL;
-  const float *WpT = head, *bp = WpT + (size_t)H * H, *WcT = bp + H, *bc = WcT + (size_t)H * 7;
-  bool compact = cls_last;
-  if (pk && !compact) {  // the samples' [CLS] rows of the final h32, in sample order
-    RowGather rg{};
-    rg.n = 1; rg.idx = cidx;
-    rg.src[0] = reinterpret_cast<const char*>(h32); rg.dst[0] = reinterpret_cast<char*>(h32c);
-    rg.sstride[0] = H * 4; rg.bytes[0] = H * 4;
-    MEC_TRY(launch_gather_rows(rg, NS, s));
-    compact = true;
-  }
-  MEC_TRY(launch_linear_mfma<BACT_TANH>(compact ? h32c : h32, compact ? (size_t)H : (size_t)L * H, NS, H, WpT, bp,
-                                        H, pooled, H, cls, H, s));
-  MEC_TRY(launch_head7(pooled, NS, H, WcT, bc, logits, probs, s));
-  return 0;
+  return text_outputs(tb, P, h32, h32c, cls_last, pooled, cls, logits, probs, s);
 }
 
 }  // namespace mec

@@ -92,25 +92,18 @@ struct TextPack {
   const int32_t *row, *off, *len;
   int ns;
 };
-// What the pack kernel writes, carved from the forward's workspace after its other buffers: per slot the
-// token id, position id and uint8 segment id, per sample its [CLS] slot (row * 128 + off).
-struct PackBufs {
-  int32_t *ids = nullptr, *pos = nullptr, *cidx = nullptr;
-  uint8_t* seg = nullptr;
-  void take(Carver& c, int M, int ns) {
-    ids = c.take<int32_t>((size_t)M);
-    pos = c.take<int32_t>((size_t)M);
-    seg = c.take<uint8_t>((size_t)M);
-    cidx = c.take<int32_t>((size_t)ns);
-  }
-};
 struct TextModel : Model {
   DevBuf emb;      // fp32 word | pos | type | ln_g | ln_b
-  DevBuf wts;      // f16 per layer: Wqkv[2304x768] Wo[768x768] Wi[3072x768] Wo2[768x3072]
-  DevBuf prm;      // fp32 per layer: bqkv bo ln1g ln1b bi bo2 ln2g ln2b ; head: WpT bp WcT bc
+  DevBuf wts;      // f16 per layer: Wqkv Wo Wi Wo2 (bert_model.h LayerWeights)
+  DevBuf prm;      // fp32 per layer: bqkv bo ln1g ln1b bi bo2 ln2g ln2b ; head: WpT bp WcT bc (bert_model.h)
   DevBuf wts32;    // fp32 path: the same GEMM weights in f32
   DevBuf ws;       // workspace
   int create(const float* blob, size_t n);
+  // The three forwards (f16: bert.hip; fp32, fp32x3: bert_f32.hip) share one shape (bert_model.h): the
+  // prologue (workspace, and for a packed batch the pack kernel), the embedding LayerNorm, then per layer
+  // the attention and the layer tail (O-projection, LN1, FFN1, FFN2, LN2). With bert_cls_last the last
+  // layer computes K | V for every token and runs its attention and that same tail on the samples' [CLS]
+  // rows only. Then the output tail (pooler, logits, probs).
   // pk (or null): the packed form -- B packed rows holding pk->ns samples, mask unused; outputs [ns, .]
   int forward(const int32_t* ids, const int32_t* mask, int B, int L, float* cls, float* logits,
               float* probs, hipStream_t s, const TextPack* pk = nullptr);
@@ -119,16 +112,19 @@ struct TextModel : Model {
                      float* cls, float* logits, float* probs, hipStream_t s);
   int forward_f32(const int32_t* ids, const int32_t* mask, int B, int L, float* cls, float* logits,
                   float* probs, hipStream_t s, const TextPack* pk = nullptr);  // bert_f32.hip
-  // fp32x3 path: wts holds the hi planes, then the lo planes (at x3_lo halfs); per GEMM B matrix
-  // (4 per layer) the epilogue scale 2^-e of its planes
+  // fp32x3 path: wts holds the hi planes, then the lo planes (at x3_lo halfs). Per layer: the
+  // activation-plane exponents (activation_exp, rigorous bounds) of LN1's and LN2's outputs, Q, K, V (= the
+  // context's) and the FFN intermediate, and per GEMM B matrix (Wqkv, Wo, Wi, Wo2) the epilogue scale
+  // 2^-e 2^(s_out - s_in): its planes' pre-scale with the activation exponents folded in. x3_s_emb: the
+  // embedding LN's exponent. x3b: bq 2^s_q | bk 2^s_k | bv 2^s_v per layer (the Wqkv planes carry the same
+  // factors)
+  struct X3Layer {
+    int s_ln1 = 0, s_ln2 = 0, s_q = 0, s_k = 0, s_v = 0, s_ffn = 0;
+    float scale[4] = {1.f, 1.f, 1.f, 1.f};
+  };
   size_t x3_lo = 0;
-  std::vector<float> x3_scale;
-  // activation-plane exponents (activation_exp, rigorous bounds): the embedding LN's, per layer LN1's,
-  // LN2's, Q's, K's, V's (= the context's) and the FFN intermediate's; x3b: bq 2^s_q | bk 2^s_k | bv 2^s_v
-  // per layer (the Wqkv planes carry the same factors). The epilogue scales in x3_scale already fold them
-  // in (2^-e 2^(s_out - s_in))
   int x3_s_emb = 0;
-  std::vector<int> x3_s_ln1, x3_s_ln2, x3_s_q, x3_s_k, x3_s_v, x3_s_ffn;
+  std::vector<X3Layer> x3_layers;
   DevBuf x3b;
   int forward_x3(const int32_t* ids, const int32_t* mask, int B, int L, float* cls, float* logits,
                  float* probs, hipStream_t s, const TextPack* pk = nullptr);  // bert_f32.hip

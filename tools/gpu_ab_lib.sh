@@ -3,6 +3,7 @@
 # alternating processes (ROUNDS each), on one encoder (ENC, PREC); the outputs of both builds are
 # compared bit for bit. Usage: ENC=image_mbv2 PREC=fp32x3 bash tools/gpu_ab_lib.sh
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
+set -o pipefail  # a timed process that fails ends the script: sed's status must not hide it
 mkdir -p gpurun_out
 ENC=${ENC:-image_mbv2}; PREC=${PREC:-fp32x3}; ROUNDS=${ROUNDS:-3}; OPT=${OPT:-gemm_autotune}; VAL=${VAL:-1}
 OUT=gpurun_out/ab_lib_${ENC}_${PREC}.txt
