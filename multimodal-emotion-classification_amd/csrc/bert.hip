@@ -1189,13 +1189,8 @@ int TextModel::create(const float* blob, size_t n) {
       }
       return mx;
     };
-    // opts.x3_plane_scale 0: every exponent 0 (the unscaled planes, A/B only)
-    // opts.x3_headroom: 2^-x3_headroom of the target (a handle re-created after a range trip)
-    auto aexp = [&](double b, double t) {
-      return opts.x3_plane_scale ? activation_exp(b, std::ldexp(t, -opts.x3_headroom)) : 0;
-    };
     double b_in = ln_bound(lg, lb);
-    x3_s_emb = aexp(b_in, kX3BoundTarget);
+    x3_s_emb = x3_exp(b_in, kX3BoundTarget);
     x3_note("emb_ln", x3_s_emb, b_in);
     x3_layers.assign(BLAYERS, X3Layer());
     std::vector<float> bq((size_t)BQKV * BLAYERS);
@@ -1211,14 +1206,14 @@ int TextModel::create(const float* blob, size_t n) {
       double bqkv3[3];
       for (int q = 0; q < 3; ++q) {
         bqkv3[q] = proj_bound(b_in, wl.wqkv + (size_t)q * BH * BH, pl.bqkv + q * BH, BH, BH);
-        sqkv[q] = aexp(bqkv3[q], kX3BoundTarget);
+        sqkv[q] = x3_exp(bqkv3[q], kX3BoundTarget);
       }
       const double b1 = ln_bound(pl.g1, pl.b1);
-      x.s_ln1 = aexp(b1, kX3BoundTarget);
+      x.s_ln1 = x3_exp(b1, kX3BoundTarget);
       const double bffn = proj_bound(b1, wl.wi, pl.bi, BI, BH);
-      x.s_ffn = aexp(bffn, kX3BoundTarget);
+      x.s_ffn = x3_exp(bffn, kX3BoundTarget);
       b_in = ln_bound(pl.g2, pl.b2);
-      x.s_ln2 = aexp(b_in, kX3BoundTarget);
+      x.s_ln2 = x3_exp(b_in, kX3BoundTarget);
       const std::string ln = "layer" + std::to_string(l) + ".";
       x3_note(ln + "q", sqkv[0], bqkv3[0]);
       x3_note(ln + "k", sqkv[1], bqkv3[1]);

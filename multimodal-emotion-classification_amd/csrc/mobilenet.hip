@@ -21,6 +21,7 @@
 #include <cmath>
 
 #include "block_ops.h"
+#include "image_pack.h"
 #include "models.h"
 
 namespace mec {
@@ -604,178 +605,16 @@ __global__ __launch_bounds__(256) void mbv2_wave_kernel(const MbArgs a, int ntil
 
 // ----------------------------------------------------------------------------- model
 
-static int pad_to(int v, int m) { return (v + m - 1) / m * m; }
-
 int MobileNetModel::create(const float* blob, size_t n) {
   if (prec == PREC_FP32) return create_f32(blob, n);  // mobilenet_f32.hip
   if (prec == PREC_FP32X3) return create_x3(blob, n);  // mobilenet_x3.hip
+  // image_pack.h: the folded stem, features[1..18] in the fused kernels' layout rounded straight to f16, head
   BlobReader rd(blob, n);
   std::vector<f16> w;
   std::vector<float> pr;
-  auto align4 = [&]() { while (pr.size() % 4) pr.push_back(0.f); };  // 16-B aligned float4 reads
-  auto bn_scale_shift = [&](int c, std::vector<double>& scale, std::vector<double>& shift) {
-    const float* g = rd.take(c);
-    const float* b = rd.take(c);
-    const float* rm = rd.take(c);
-    const float* rv = rd.take(c);
-    scale.assign(c, 0.0);
-    shift.assign(c, 0.0);
-    if (!rd.ok) return;
-    for (int i = 0; i < c; ++i) {
-      scale[i] = (double)g[i] / std::sqrt((double)rv[i] + 1e-5);
-      shift[i] = (double)b[i] - (double)rm[i] * scale[i];
-    }
-  };
-  std::vector<double> sc, sh;
-  // ---- stem features[0]: conv 3x3/2 (3 -> 32) + BN + ReLU6. ToTensor (/255) and Normalize
-  // fold into per-pixel weights; the -mean/std term of the in-image taps becomes a bias per
-  // border class (stem row 0 / col 0 lose their top / left taps; 224 = 2*112 so the bottom /
-  // right taps are always inside).
-  {
-    const float* src = rd.take((size_t)32 * 3 * 9);
-    bn_scale_shift(32, sc, sh);
-    align4();
-    stem_w_off = pr.size();
-    pr.resize(pr.size() + 9 * 32, 0.f);
-    stem_rgb_off = pr.size();
-    pr.resize(pr.size() + 27 * 32, 0.f);
-    stem_corr_off = pr.size();
-    pr.resize(pr.size() + 4 * 32, 0.f);
-    const double mean[3] = {0.485, 0.456, 0.406}, stdv[3] = {0.229, 0.224, 0.225};
-    if (rd.ok) {
-      for (int o = 0; o < 32; ++o) {
-        double cterm[9] = {};
-        for (int t = 0; t < 9; ++t) {
-          double gsum = 0.0;
-          for (int c = 0; c < 3; ++c) {
-            const double wv = src[((size_t)o * 3 + c) * 9 + t];
-            const double mf = (double)(float)mean[c], sf = (double)(float)stdv[c];
-            gsum += wv / (255.0 * sf);
-            cterm[t] -= wv * mf / sf;
-            pr[stem_rgb_off + (size_t)(c * 9 + t) * 32 + o] = (float)(wv / (255.0 * sf) * sc[o]);
-          }
-          pr[stem_w_off + (size_t)t * 32 + o] = (float)(gsum * sc[o]);
-        }
-        for (int cls = 0; cls < 4; ++cls) {  // cls = 2 * (row 0) + (col 0)
-          double sum = sh[o];
-          for (int t = 0; t < 9; ++t) {
-            const int ky = t / 3, kx = t % 3;
-            if (((cls & 2) && ky == 0) || ((cls & 1) && kx == 0)) continue;
-            sum += cterm[t] * sc[o];
-          }
-          pr[stem_corr_off + (size_t)cls * 32 + o] = (float)sum;
-        }
-      }
-    }
-  }
-  // ---- inverted-residual blocks features[1..17]
-  static const int kSet[7][4] = {{1, 16, 1, 1}, {6, 24, 2, 2}, {6, 32, 3, 2}, {6, 64, 4, 2},
-                                 {6, 96, 3, 1}, {6, 160, 3, 2}, {6, 320, 1, 1}};
-  blocks.clear();
-  int cin = 32, prev_lcoutp = 32;
-  for (int si = 0; si < 7; ++si)
-    for (int r = 0; r < kSet[si][2]; ++r) {
-      MbBlock b;
-      b.t = kSet[si][0]; b.cin = cin; b.hid = cin * b.t; b.cout = kSet[si][1]; b.stride = r == 0 ? kSet[si][3] : 1;
-      b.cinp = pad_to(cin, 32); b.hidp = pad_to(b.hid, 32); b.coutp = pad_to(b.cout, 16);
-      if (b.t != 1) {  // expand 1x1 + BN (+ ReLU6)
-        const float* we = rd.take((size_t)b.hid * cin);
-        bn_scale_shift(b.hid, sc, sh);
-        b.we_off = w.size();
-        w.resize(w.size() + (size_t)b.hidp * b.cinp, (f16)0.f);
-        align4();
-        b.be_off = pr.size();
-        pr.resize(pr.size() + b.hidp, 0.f);
-        if (rd.ok)
-          for (int h = 0; h < b.hid; ++h) {
-            for (int c = 0; c < cin; ++c) w[b.we_off + (size_t)h * b.cinp + c] = (f16)((double)we[(size_t)h * cin + c] * sc[h]);
-            pr[b.be_off + h] = (float)sh[h];
-          }
-      }
-      {  // depthwise 3x3 + BN (+ ReLU6): fp32 [hidp/8][9 taps][8 channels]
-        const float* wd = rd.take((size_t)b.hid * 9);
-        bn_scale_shift(b.hid, sc, sh);
-        align4();
-        b.wd_off = pr.size();
-        pr.resize(pr.size() + (size_t)b.hidp * 9, 0.f);
-        b.bd_off = pr.size();
-        pr.resize(pr.size() + b.hidp, 0.f);
-        if (rd.ok)
-          for (int h = 0; h < b.hid; ++h) {
-            for (int t = 0; t < 9; ++t)
-              pr[b.wd_off + (size_t)(h / 8) * 72 + t * 8 + (h % 8)] = (float)((double)wd[(size_t)h * 9 + t] * sc[h]);
-            pr[b.bd_off + h] = (float)sh[h];
-          }
-      }
-      {  // project 1x1 + BN (linear bottleneck)
-        const float* wp = rd.take((size_t)b.cout * b.hid);
-        bn_scale_shift(b.cout, sc, sh);
-        b.wp_off = w.size();
-        w.resize(w.size() + (size_t)b.coutp * b.hidp, (f16)0.f);
-        align4();
-        b.bp_off = pr.size();
-        pr.resize(pr.size() + b.coutp, 0.f);
-        if (rd.ok)
-          for (int o = 0; o < b.cout; ++o) {
-            for (int h = 0; h < b.hid; ++h)
-              w[b.wp_off + (size_t)o * b.hidp + h] = (f16)((double)wp[(size_t)o * b.hid + h] * sc[o]);
-            pr[b.bp_off + o] = (float)sh[o];
-          }
-      }
-      b.lcinp = prev_lcoutp;
-      b.lcoutp = pad_to(b.cout, 64);
-      prev_lcoutp = b.lcoutp;
-      if (b.t != 1 && b.hidp % 64 == 0) {  // layered form: the same matrices, K / N padded with zeros
-        b.lwe_off = w.size();
-        w.resize(w.size() + (size_t)b.hidp * b.lcinp, (f16)0.f);
-        for (int h = 0; h < b.hidp; ++h)
-          for (int c = 0; c < b.cinp && c < b.lcinp; ++c)
-            w[b.lwe_off + (size_t)h * b.lcinp + c] = w[b.we_off + (size_t)h * b.cinp + c];
-        b.lwp_off = w.size();
-        w.resize(w.size() + (size_t)b.lcoutp * b.hidp, (f16)0.f);
-        std::copy(w.begin() + b.wp_off, w.begin() + b.wp_off + (size_t)b.coutp * b.hidp, w.begin() + b.lwp_off);
-        align4();
-        b.lbp_off = pr.size();
-        pr.resize(pr.size() + b.lcoutp, 0.f);
-        std::copy(pr.begin() + b.bp_off, pr.begin() + b.bp_off + b.coutp, pr.begin() + b.lbp_off);
-      }
-      blocks.push_back(b);
-      cin = b.cout;
-    }
-  // ---- features[18]: 1x1 320 -> 1280 + BN + ReLU6 (GEMM engine)
-  {
-    const float* wl = rd.take((size_t)1280 * 320);
-    bn_scale_shift(1280, sc, sh);
-    last_w_off = w.size();
-    w.resize(w.size() + (size_t)1280 * 320, (f16)0.f);
-    align4();
-    last_b_off = pr.size();
-    pr.resize(pr.size() + 1280, 0.f);
-    if (rd.ok)
-      for (int o = 0; o < 1280; ++o) {
-        for (int c = 0; c < 320; ++c) w[last_w_off + (size_t)o * 320 + c] = (f16)((double)wl[(size_t)o * 320 + c] * sc[o]);
-        pr[last_b_off + o] = (float)sh[o];
-      }
-  }
-  // ---- head: classifier[1] Linear(1280,512), classifier[4] Linear(512,7), fp32 [K][N]
-  const float* f1w = rd.take((size_t)512 * 1280);
-  const float* f1b = rd.take(512);
-  const float* f2w = rd.take((size_t)7 * 512);
-  const float* f2b = rd.take(7);
-  MEC_REQUIRE(rd.ok && rd.off == n, "image_mbv2 blob size mismatch");
-  align4();
-  fc1_off = pr.size();
-  pr.resize(pr.size() + (size_t)1280 * 512);
-  for (int i = 0; i < 1280; ++i)
-    for (int j = 0; j < 512; ++j) pr[fc1_off + (size_t)i * 512 + j] = f1w[(size_t)j * 1280 + i];
-  fc1b_off = pr.size();
-  pr.insert(pr.end(), f1b, f1b + 512);
-  fc2_off = pr.size();
-  pr.resize(pr.size() + 512 * 7);
-  for (int i = 0; i < 512; ++i)
-    for (int j = 0; j < 7; ++j) pr[fc2_off + (size_t)i * 7 + j] = f2w[(size_t)j * 512 + i];
-  fc2b_off = pr.size();
-  pr.insert(pr.end(), f2b, f2b + 7);
+  pack_mbv2_stem_folded(rd, pr, stem_w_off, stem_rgb_off, stem_corr_off);
+  pack_mbv2_body(rd, kMbFused, w, pr, blocks, last_w_off, last_b_off);
+  MEC_REQUIRE(pack_head(rd, 1280, pr, fc1_off, fc1b_off, fc2_off, fc2b_off), "image_mbv2 blob size mismatch");
   MEC_TRY(upload(wts, w.data(), w.size() * sizeof(f16)));
   MEC_TRY(upload(prm, pr.data(), pr.size() * sizeof(float)));
   return 0;

@@ -16,13 +16,13 @@
 #include <cmath>
 
 #include "block_ops.h"
+#include "image_pack.h"
 #include "models.h"
 
 namespace mec {
 
 namespace {
 constexpr int MB_STEM_K = 32;  // 27 taps padded to a 32-float K tile
-int pad64(int v) { return (v + 63) / 64 * 64; }
 }  // namespace
 
 // stem im2col: one thread per 4 consecutive k of one 112 x 112 output pixel's row
@@ -92,121 +92,22 @@ __global__ __launch_bounds__(256) void mbv2_dw_f32_kernel(const float* __restric
 int MobileNetModel::create_f32(const float* blob, size_t n) {
   BlobReader rd(blob, n);
   std::vector<float> w, pr;
-  auto bn = [&](int c, std::vector<double>& scale, std::vector<double>& shift) {
-    const float* g = rd.take(c);
-    const float* b = rd.take(c);
-    const float* rm = rd.take(c);
-    const float* rv = rd.take(c);
-    scale.assign(c, 0.0);
-    shift.assign(c, 0.0);
-    if (!rd.ok) return;
-    for (int i = 0; i < c; ++i) {
-      scale[i] = (double)g[i] / std::sqrt((double)rv[i] + 1e-5);
-      shift[i] = (double)b[i] - (double)rm[i] * scale[i];
-    }
-  };
-  auto align4 = [&](std::vector<float>& v) { while (v.size() % 4) v.push_back(0.f); };
-  std::vector<double> sc, sh;
-  {  // stem [64][32] (32 real output channels, k = c*9 + kh*3 + kw), bias [64]
+  {  // stem [64][32] (32 real output channels, k = c*9 + kh*3 + kw), bias [64] (at stem_corr_off)
     const float* src = rd.take((size_t)32 * 27);
-    bn(32, sc, sh);
+    const BnFold bn = bn_fold(rd, 32);
     stem_w_off = w.size();
     w.resize(w.size() + (size_t)64 * MB_STEM_K, 0.f);
     align4(pr);
-    stem_corr_off = pr.size();  // fp32 path: the stem bias
+    stem_corr_off = pr.size();
     pr.resize(pr.size() + 64, 0.f);
     if (rd.ok)
       for (int o = 0; o < 32; ++o) {
-        for (int k = 0; k < 27; ++k) w[stem_w_off + (size_t)o * MB_STEM_K + k] = (float)((double)src[o * 27 + k] * sc[o]);
-        pr[stem_corr_off + o] = (float)sh[o];
+        for (int k = 0; k < 27; ++k) w[stem_w_off + (size_t)o * MB_STEM_K + k] = (float)((double)src[o * 27 + k] * bn.scale[o]);
+        pr[stem_corr_off + o] = (float)bn.shift[o];
       }
   }
-  static const int kSet[7][4] = {{1, 16, 1, 1}, {6, 24, 2, 2}, {6, 32, 3, 2}, {6, 64, 4, 2},
-                                 {6, 96, 3, 1}, {6, 160, 3, 2}, {6, 320, 1, 1}};
-  blocks.clear();
-  int cin = 32;
-  for (int si = 0; si < 7; ++si)
-    for (int r = 0; r < kSet[si][2]; ++r) {
-      MbBlock b;
-      b.t = kSet[si][0]; b.cin = cin; b.hid = cin * b.t; b.cout = kSet[si][1]; b.stride = r == 0 ? kSet[si][3] : 1;
-      b.cinp = pad64(cin); b.hidp = pad64(b.hid); b.coutp = pad64(b.cout);
-      if (b.t != 1) {  // expand [hidp][cinp], bias [hidp]
-        const float* we = rd.take((size_t)b.hid * cin);
-        bn(b.hid, sc, sh);
-        b.we_off = w.size();
-        w.resize(w.size() + (size_t)b.hidp * b.cinp, 0.f);
-        align4(pr);
-        b.be_off = pr.size();
-        pr.resize(pr.size() + b.hidp, 0.f);
-        if (rd.ok)
-          for (int h = 0; h < b.hid; ++h) {
-            for (int c = 0; c < cin; ++c) w[b.we_off + (size_t)h * b.cinp + c] = (float)((double)we[(size_t)h * cin + c] * sc[h]);
-            pr[b.be_off + h] = (float)sh[h];
-          }
-      }
-      {  // depthwise [9][hidp], bias [hidp]
-        const float* wd = rd.take((size_t)b.hid * 9);
-        bn(b.hid, sc, sh);
-        align4(pr);
-        b.wd_off = pr.size();
-        pr.resize(pr.size() + (size_t)9 * b.hidp, 0.f);
-        b.bd_off = pr.size();
-        pr.resize(pr.size() + b.hidp, 0.f);
-        if (rd.ok)
-          for (int h = 0; h < b.hid; ++h) {
-            for (int t = 0; t < 9; ++t) pr[b.wd_off + (size_t)t * b.hidp + h] = (float)((double)wd[(size_t)h * 9 + t] * sc[h]);
-            pr[b.bd_off + h] = (float)sh[h];
-          }
-      }
-      {  // project [coutp][hidp], bias [coutp]
-        const float* wp = rd.take((size_t)b.cout * b.hid);
-        bn(b.cout, sc, sh);
-        b.wp_off = w.size();
-        w.resize(w.size() + (size_t)b.coutp * b.hidp, 0.f);
-        align4(pr);
-        b.bp_off = pr.size();
-        pr.resize(pr.size() + b.coutp, 0.f);
-        if (rd.ok)
-          for (int o = 0; o < b.cout; ++o) {
-            for (int h = 0; h < b.hid; ++h) w[b.wp_off + (size_t)o * b.hidp + h] = (float)((double)wp[(size_t)o * b.hid + h] * sc[o]);
-            pr[b.bp_off + o] = (float)sh[o];
-          }
-      }
-      blocks.push_back(b);
-      cin = b.cout;
-    }
-  {  // features[18]: [1280][320]
-    const float* wl = rd.take((size_t)1280 * 320);
-    bn(1280, sc, sh);
-    last_w_off = w.size();
-    w.resize(w.size() + (size_t)1280 * 320, 0.f);
-    align4(pr);
-    last_b_off = pr.size();
-    pr.resize(pr.size() + 1280, 0.f);
-    if (rd.ok)
-      for (int o = 0; o < 1280; ++o) {
-        for (int c = 0; c < 320; ++c) w[last_w_off + (size_t)o * 320 + c] = (float)((double)wl[(size_t)o * 320 + c] * sc[o]);
-        pr[last_b_off + o] = (float)sh[o];
-      }
-  }
-  const float* f1w = rd.take((size_t)512 * 1280);
-  const float* f1b = rd.take(512);
-  const float* f2w = rd.take((size_t)7 * 512);
-  const float* f2b = rd.take(7);
-  MEC_REQUIRE(rd.ok && rd.off == n, "image_mbv2 blob size mismatch");
-  align4(pr);
-  fc1_off = pr.size();
-  pr.resize(pr.size() + (size_t)1280 * 512);
-  for (int i = 0; i < 1280; ++i)
-    for (int j = 0; j < 512; ++j) pr[fc1_off + (size_t)i * 512 + j] = f1w[(size_t)j * 1280 + i];
-  fc1b_off = pr.size();
-  pr.insert(pr.end(), f1b, f1b + 512);
-  fc2_off = pr.size();
-  pr.resize(pr.size() + 512 * 7);
-  for (int i = 0; i < 512; ++i)
-    for (int j = 0; j < 7; ++j) pr[fc2_off + (size_t)i * 7 + j] = f2w[(size_t)j * 512 + i];
-  fc2b_off = pr.size();
-  pr.insert(pr.end(), f2b, f2b + 7);
+  pack_mbv2_body(rd, kMbF32, w, pr, blocks, last_w_off, last_b_off);  // image_pack.h
+  MEC_REQUIRE(pack_head(rd, 1280, pr, fc1_off, fc1b_off, fc2_off, fc2b_off), "image_mbv2 blob size mismatch");
   MEC_TRY(upload(wts32, w.data(), w.size() * sizeof(float)));
   MEC_TRY(upload(prm, pr.data(), pr.size() * sizeof(float)));
   return 0;

@@ -16,6 +16,7 @@
 #include <cmath>
 
 #include "block_ops.h"
+#include "image_pack.h"
 #include "models.h"
 
 namespace mec {
@@ -636,178 +637,17 @@ int dispatch_x3_block(const MbBlock& b, const MbX3Args& a, int B, int stem_c, hi
 int MobileNetModel::create_x3(const float* blob, size_t n) {
   BlobReader rd(blob, n);
   std::vector<float> w, pr;
-  auto align4 = [&]() { while (pr.size() % 4) pr.push_back(0.f); };
-  auto pad_to = [](int v, int m) { return (v + m - 1) / m * m; };
-  double est = 0.0;  // the last BN's output estimate, max_c |beta_c| + 6 |gamma_c| (activation_exp)
-  auto bn_scale_shift = [&](int c, std::vector<double>& scale, std::vector<double>& shift) {
-    const float* g = rd.take(c);
-    const float* b = rd.take(c);
-    const float* rm = rd.take(c);
-    const float* rv = rd.take(c);
-    scale.assign(c, 0.0);
-    shift.assign(c, 0.0);
-    est = 0.0;
-    if (!rd.ok) return;
-    for (int i = 0; i < c; ++i) {
-      scale[i] = (double)g[i] / std::sqrt((double)rv[i] + 1e-5);
-      shift[i] = (double)b[i] - (double)rm[i] * scale[i];
-      est = std::max(est, std::fabs((double)b[i]) + 6.0 * std::fabs((double)g[i]));
-    }
-  };
-  std::vector<double> sc, sh;
-  {  // stem, as MobileNetModel::create (mobilenet.hip)
-    const float* src = rd.take((size_t)32 * 3 * 9);
-    bn_scale_shift(32, sc, sh);
-    align4();
-    stem_w_off = pr.size();
-    pr.resize(pr.size() + 9 * 32, 0.f);
-    stem_rgb_off = pr.size();
-    pr.resize(pr.size() + 27 * 32, 0.f);
-    stem_corr_off = pr.size();
-    pr.resize(pr.size() + 4 * 32, 0.f);
-    const double mean[3] = {0.485, 0.456, 0.406}, stdv[3] = {0.229, 0.224, 0.225};
-    if (rd.ok)
-      for (int o = 0; o < 32; ++o) {
-        double cterm[9] = {};
-        for (int t = 0; t < 9; ++t) {
-          double gsum = 0.0;
-          for (int c = 0; c < 3; ++c) {
-            const double wv = src[((size_t)o * 3 + c) * 9 + t];
-            const double mf = (double)(float)mean[c], sf = (double)(float)stdv[c];
-            gsum += wv / (255.0 * sf);
-            cterm[t] -= wv * mf / sf;
-            pr[stem_rgb_off + (size_t)(c * 9 + t) * 32 + o] = (float)(wv / (255.0 * sf) * sc[o]);
-          }
-          pr[stem_w_off + (size_t)t * 32 + o] = (float)(gsum * sc[o]);
-        }
-        for (int cls = 0; cls < 4; ++cls) {
-          double sum = sh[o];
-          for (int t = 0; t < 9; ++t) {
-            const int ky = t / 3, kx = t % 3;
-            if (((cls & 2) && ky == 0) || ((cls & 1) && kx == 0)) continue;
-            sum += cterm[t] * sc[o];
-          }
-          pr[stem_corr_off + (size_t)cls * 32 + o] = (float)sum;
-        }
-      }
-  }
-  static const int kSet[7][4] = {{1, 16, 1, 1}, {6, 24, 2, 2}, {6, 32, 3, 2}, {6, 64, 4, 2},
-                                 {6, 96, 3, 1}, {6, 160, 3, 2}, {6, 320, 1, 1}};
-  blocks.clear();
+  pack_mbv2_stem_folded(rd, pr, stem_w_off, stem_rgb_off, stem_corr_off);  // image_pack.h
+  pack_mbv2_body(rd, kMbFused, w, pr, blocks, last_w_off, last_b_off);
+  MEC_REQUIRE(pack_head(rd, 1280, pr, fc1_off, fc1b_off, fc2_off, fc2b_off), "image_mbv2 blob size mismatch");
   x3_scale.clear();
   lx3_scale.clear();
-  int cin = 32, prev_lcoutp = 32;
-  for (int si = 0; si < 7; ++si)
-    for (int r = 0; r < kSet[si][2]; ++r) {
-      MbBlock b;
-      b.t = kSet[si][0]; b.cin = cin; b.hid = cin * b.t; b.cout = kSet[si][1]; b.stride = r == 0 ? kSet[si][3] : 1;
-      b.cinp = pad_to(cin, 32); b.hidp = pad_to(b.hid, 32); b.coutp = pad_to(b.cout, 16);
-      if (b.t != 1) {
-        const float* we = rd.take((size_t)b.hid * cin);
-        bn_scale_shift(b.hid, sc, sh);
-        b.we_off = w.size();
-        w.resize(w.size() + (size_t)b.hidp * b.cinp, 0.f);
-        align4();
-        b.be_off = pr.size();
-        pr.resize(pr.size() + b.hidp, 0.f);
-        if (rd.ok)
-          for (int h = 0; h < b.hid; ++h) {
-            for (int c = 0; c < cin; ++c) w[b.we_off + (size_t)h * b.cinp + c] = (float)((double)we[(size_t)h * cin + c] * sc[h]);
-            pr[b.be_off + h] = (float)sh[h];
-          }
-      }
-      {
-        const float* wd = rd.take((size_t)b.hid * 9);
-        bn_scale_shift(b.hid, sc, sh);
-        align4();
-        b.wd_off = pr.size();
-        pr.resize(pr.size() + (size_t)b.hidp * 9, 0.f);
-        b.bd_off = pr.size();
-        pr.resize(pr.size() + b.hidp, 0.f);
-        if (rd.ok)
-          for (int h = 0; h < b.hid; ++h) {
-            for (int t = 0; t < 9; ++t)
-              pr[b.wd_off + (size_t)(h / 8) * 72 + t * 8 + (h % 8)] = (float)((double)wd[(size_t)h * 9 + t] * sc[h]);
-            pr[b.bd_off + h] = (float)sh[h];
-          }
-      }
-      {
-        const float* wp = rd.take((size_t)b.cout * b.hid);
-        bn_scale_shift(b.cout, sc, sh);
-        b.x3_est = est;
-        b.wp_off = w.size();
-        w.resize(w.size() + (size_t)b.coutp * b.hidp, 0.f);
-        align4();
-        b.bp_off = pr.size();
-        pr.resize(pr.size() + b.coutp, 0.f);
-        if (rd.ok)
-          for (int o = 0; o < b.cout; ++o) {
-            for (int h = 0; h < b.hid; ++h) w[b.wp_off + (size_t)o * b.hidp + h] = (float)((double)wp[(size_t)o * b.hid + h] * sc[o]);
-            pr[b.bp_off + o] = (float)sh[o];
-          }
-      }
-      b.lcinp = prev_lcoutp;
-      b.lcoutp = pad_to(b.cout, 64);
-      prev_lcoutp = b.lcoutp;
-      if (b.t != 1 && b.hidp % 64 == 0) {  // layered form: the same matrices, K / N padded with zeros
-        b.lwe_off = w.size();
-        w.resize(w.size() + (size_t)b.hidp * b.lcinp, 0.f);
-        for (int h = 0; h < b.hidp; ++h)
-          for (int c = 0; c < b.cinp && c < b.lcinp; ++c)
-            w[b.lwe_off + (size_t)h * b.lcinp + c] = w[b.we_off + (size_t)h * b.cinp + c];
-        b.lwp_off = w.size();
-        w.resize(w.size() + (size_t)b.lcoutp * b.hidp, 0.f);
-        std::copy(w.begin() + b.wp_off, w.begin() + b.wp_off + (size_t)b.coutp * b.hidp, w.begin() + b.lwp_off);
-        b.lbp_off = pr.size();
-        pr.resize(pr.size() + b.lcoutp, 0.f);
-        std::copy(pr.begin() + b.bp_off, pr.begin() + b.bp_off + b.coutp, pr.begin() + b.lbp_off);
-      }
-      blocks.push_back(b);
-      cin = b.cout;
-    }
-  {  // features[18]: [1280][320]
-    const float* wl = rd.take((size_t)1280 * 320);
-    bn_scale_shift(1280, sc, sh);
-    last_w_off = w.size();
-    w.resize(w.size() + (size_t)1280 * 320, 0.f);
-    align4();
-    last_b_off = pr.size();
-    pr.resize(pr.size() + 1280, 0.f);
-    if (rd.ok)
-      for (int o = 0; o < 1280; ++o) {
-        for (int c = 0; c < 320; ++c) w[last_w_off + (size_t)o * 320 + c] = (float)((double)wl[(size_t)o * 320 + c] * sc[o]);
-        pr[last_b_off + o] = (float)sh[o];
-      }
-  }
-  const float* f1w = rd.take((size_t)512 * 1280);
-  const float* f1b = rd.take(512);
-  const float* f2w = rd.take((size_t)7 * 512);
-  const float* f2b = rd.take(7);
-  MEC_REQUIRE(rd.ok && rd.off == n, "image_mbv2 blob size mismatch");
-  align4();
-  fc1_off = pr.size();
-  pr.resize(pr.size() + (size_t)1280 * 512);
-  for (int i = 0; i < 1280; ++i)
-    for (int j = 0; j < 512; ++j) pr[fc1_off + (size_t)i * 512 + j] = f1w[(size_t)j * 1280 + i];
-  fc1b_off = pr.size();
-  pr.insert(pr.end(), f1b, f1b + 512);
-  fc2_off = pr.size();
-  pr.resize(pr.size() + 512 * 7);
-  for (int i = 0; i < 512; ++i)
-    for (int j = 0; j < 7; ++j) pr[fc2_off + (size_t)i * 7 + j] = f2w[(size_t)j * 512 + i];
-  fc2b_off = pr.size();
-  pr.insert(pr.end(), f2b, f2b + 7);
-  // Activation-plane exponents (activation_exp, BN estimates): one per stage (a (t, c, n, s) setting:
+  // Activation-plane exponents (x3_exp, BN estimates): one per stage (a (t, c, n, s) setting:
   // its first block is the only one without a residual, so a stage's outputs -- a residual block's output
   // and its input -- share it), the stage estimate being the running sum of the projection BN estimates
   // along the residual chain. Block inputs are the previous stage's planes; the depthwise outputs are at
   // kDwUp. Every epilogue scale below folds in 2^(s_out - s_in) (the fused blocks' and the expand GEMMs'
   // outputs are f32: s_out = 0 there).
-  // opts.x3_plane_scale 0: every exponent 0 (the unscaled planes, A/B only)
-  // opts.x3_headroom: 2^-x3_headroom of the target (a handle re-created after a range trip)
-  auto aexp = [&](double b, double t) {
-    return opts.x3_plane_scale ? activation_exp(b, std::ldexp(t, -opts.x3_headroom)) : 0;
-  };
   {
     int s_prev = 0;
     for (size_t b0 = 0; b0 < blocks.size();) {
@@ -818,7 +658,7 @@ int MobileNetModel::create_x3(const float* blob, size_t n) {
         e = blocks[i].x3_est + (i > b0 ? e : 0.0);
         e_max = std::max(e_max, e);
       }
-      const int st = aexp(e_max, kX3EstimateTarget);
+      const int st = x3_exp(e_max, kX3EstimateTarget);
       x3_note("features" + std::to_string(b0 + 1) + "-" + std::to_string(b1) + ".out", st, e_max);
       for (size_t i = b0; i < b1; ++i) {
         blocks[i].x3_s_in = i == b0 ? s_prev : st;
@@ -830,7 +670,7 @@ int MobileNetModel::create_x3(const float* blob, size_t n) {
   }
   for (MbBlock& b : blocks)
     if (b.lwe_off) {
-      align4();
+      align4(pr);
       b.lbp_x3_off = pr.size();
       for (int o = 0; o < b.lcoutp; ++o) pr.push_back(std::ldexp(pr[b.lbp_off + o], b.x3_s_out));
     }

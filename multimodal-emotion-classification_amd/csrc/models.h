@@ -36,6 +36,9 @@ struct Model {
   // bound=<bound or BN estimate>" plus the headroom the exponents were chosen with (mec_model_x3_report)
   std::string x3_report;
   void x3_note(const std::string& name, int s, double bound);
+  // the exponent this handle gives an activation tensor: activation_exp (below) against 2^-x3_headroom of
+  // the target (a handle re-created after a range trip), or 0 with x3_plane_scale off (unscaled planes, A/B only)
+  int x3_exp(double bound, double target) const;
   virtual ~Model();
   // errors a kernel could only report after the fact (mec_model_check): 0 = none since the last
   // check. Call after the stream that ran the handle's forwards has been synchronized.
@@ -209,7 +212,7 @@ struct ImageNet : Model {
 
 // ---------------------------------------------------------------- ResNet50 + head
 struct ConvLayer {
-  size_t w_off = 0;   // f16 [Cout][kh][kw][Cin] (BN scale folded)
+  size_t w_off = 0;   // [Cout][kh][kw][Cin] (BN scale folded; image_pack.h pack_conv)
   size_t b_off = 0;   // f32 [Cout] (BN shift)
   int cin = 0, cout = 0, ks = 1, stride = 1, pad = 0;
   // fp32x3 path: the epilogue scale 2^-e 2^(x3_s - s_in) (weight planes' pre-scale, activation-plane
@@ -258,13 +261,13 @@ struct ImageModel : ImageNet {
 };
 
 // ---------------------------------------------------------------- MobileNetV2 + head
-// One inverted-residual block (features[1..17]) as packed for mbv2_block_kernel: channel
-// counts padded (cin -> cinp % 32, hidden -> hidp % 32, cout -> coutp % 16) with zero weights.
+// One inverted-residual block (features[1..17]) as image_pack.h packs it (pack_mbv2_body): channel counts
+// padded with zero weights per precision (MbLayout: 32 / 32 / 16 for the fused kernels, 64 on the fp32 path).
 struct MbBlock {
   int t = 1, cin = 0, hid = 0, cout = 0, stride = 1;
   int cinp = 0, hidp = 0, coutp = 0;
   size_t we_off = 0, wp_off = 0;          // f16: expand [hidp][cinp], project [coutp][hidp]
-  size_t be_off = 0, wd_off = 0, bd_off = 0, bp_off = 0;  // f32: expand bias, dw [hidp/8][9][8], dw bias, project bias
+  size_t be_off = 0, wd_off = 0, bd_off = 0, bp_off = 0;  // f32: expand bias, dw (MbLayout), dw bias, project bias
   // fp32x3 layered form (hidp % 64 == 0): expand [hidp][lcinp], project [lcoutp][hidp] (lcoutp = cout padded
   // to 64, lcinp = the previous block's lcoutp), project bias [lcoutp]
   int lcinp = 0, lcoutp = 0;
@@ -280,7 +283,9 @@ struct MobileNetModel : ImageNet {
   DevBuf wts;   // f16 1x1 weights
   DevBuf prm;   // fp32 stem, depthwise weights, biases, head
   DevBuf ws;    // workspace
-  size_t stem_w_off = 0, stem_rgb_off = 0, stem_corr_off = 0;  // f32 [9][32], [3*9][32], [4 classes][32]
+  // f32 [9][32], [3*9][32], [4 border classes][32] (image_pack.h pack_mbv2_stem_folded); fp32 path: stem_w_off
+  // in wts32, [64][32] im2col weights, and stem_corr_off the stem bias [64]
+  size_t stem_w_off = 0, stem_rgb_off = 0, stem_corr_off = 0;
   std::vector<MbBlock> blocks;
   size_t last_w_off = 0, last_b_off = 0;  // features[18]: f16 [1280][320], f32 [1280]
   size_t fc1_off = 0, fc1b_off = 0, fc2_off = 0, fc2b_off = 0;

@@ -6,6 +6,7 @@
 #include <cmath>
 
 #include "block_ops.h"
+#include "image_pack.h"
 #include "models.h"
 
 namespace mec {
@@ -358,8 +359,6 @@ __global__ __launch_bounds__(256, 2) void stem_pool_kernel(const uint8_t* __rest
 // AdaptiveAvgPool2d(1) on NHWC f16 -> f32 [B, C]: one thread per (sample, channel).
 
 // ----------------------------------------------------------------------------- model
-static const int kLayers[4][3] = {{64, 3, 1}, {128, 4, 2}, {256, 6, 2}, {512, 3, 2}};
-
 int ImageModel::create(const float* blob, size_t n) {
   if (prec == PREC_FP32 || prec == PREC_FP32X3) {  // resnet_f32.hip
     MEC_TRY(create_f32(blob, n));
@@ -368,44 +367,13 @@ int ImageModel::create(const float* blob, size_t n) {
   BlobReader rd(blob, n);
   std::vector<f16> w;
   std::vector<float> pr;
-  auto bn_fold = [&](int c, std::vector<float>& scale) {  // -> bias offset in pr
-    const float* g = rd.take(c);
-    const float* b = rd.take(c);
-    const float* rm = rd.take(c);
-    const float* rv = rd.take(c);
-    scale.resize(c);
-    size_t off = pr.size();
-    for (int i = 0; i < c; ++i) {
-      const double s = (double)g[i] / std::sqrt((double)rv[i] + 1e-5);
-      scale[i] = (float)s;
-      pr.push_back((float)((double)b[i] - (double)rm[i] * s));
-    }
-    return off;
-  };
-  auto conv = [&](int cout, int cin, int ks, int stride, int pad) {
-    ConvLayer L;
-    L.cin = cin; L.cout = cout; L.ks = ks; L.stride = stride; L.pad = pad;
-    const float* src = rd.take((size_t)cout * cin * ks * ks);
-    std::vector<float> scale;
-    L.b_off = bn_fold(cout, scale);
-    L.w_off = w.size();
-    w.resize(w.size() + (size_t)cout * cin * ks * ks);
-    if (!rd.ok) return L;
-    for (int o = 0; o < cout; ++o)
-      for (int kh = 0; kh < ks; ++kh)
-        for (int kw = 0; kw < ks; ++kw)
-          for (int c = 0; c < cin; ++c)
-            w[L.w_off + (((size_t)o * ks + kh) * ks + kw) * cin + c] =
-                (f16)((double)src[(((size_t)o * cin + c) * ks + kh) * ks + kw] * scale[o]);
-    return L;
-  };
   // stem (stem_pool_kernel): ToTensor(/255) + Normalize + BN scale folded into per-channel
   // pixel weights (gray: the three replicated channels summed into one); the -mean/std
   // term summed over in-image taps goes to a [16 border classes][64] table.
   {
     const float* src = rd.take((size_t)64 * 3 * 49);
-    std::vector<float> scale;
-    stem.b_off = bn_fold(64, scale);
+    const BnFold bn = bn_fold(rd, 64);
+    stem.b_off = append_shift(pr, bn);
     stem.cin = 1; stem.cout = 64; stem.ks = 7; stem.stride = 2; stem.pad = 3;
     stem_rgb = stem;
     stem_rgb.cin = 3;
@@ -418,7 +386,8 @@ int ImageModel::create(const float* blob, size_t n) {
     const double mean[3] = {0.485, 0.456, 0.406}, stdv[3] = {0.229, 0.224, 0.225};
     if (rd.ok) {
       std::vector<double> c0(64 * 49);
-      for (int o = 0; o < 64; ++o)
+      for (int o = 0; o < 64; ++o) {
+        const double so = (double)(float)bn.scale[o];  // the float-rounded scale, as pack_conv
         for (int t = 0; t < 49; ++t) {
           double a = 0.0, cc = 0.0;
           for (int c = 0; c < 3; ++c) {
@@ -426,11 +395,12 @@ int ImageModel::create(const float* blob, size_t n) {
             const double mf = (double)(float)mean[c], sf = (double)(float)stdv[c];
             a += wv / (255.0 * sf);
             cc -= wv * mf / sf;
-            w[stem_rgb.w_off + (size_t)o * 192 + 64 * c + (t / 7) * 8 + t % 7] = (f16)(wv / (255.0 * sf) * scale[o]);
+            w[stem_rgb.w_off + (size_t)o * 192 + 64 * c + (t / 7) * 8 + t % 7] = (f16)(wv / (255.0 * sf) * so);
           }
-          w[stem.w_off + (size_t)o * 64 + (t / 7) * 8 + t % 7] = (f16)(a * scale[o]);  // k = kh*8 + kw
-          c0[o * 49 + t] = cc * scale[o];
+          w[stem.w_off + (size_t)o * 64 + (t / 7) * 8 + t % 7] = (f16)(a * so);  // k = kh*8 + kw
+          c0[o * 49 + t] = cc * so;
         }
+      }
       // border classes of a stem coordinate: 0, 1, interior, 111 (see sp_cls)
       const int rep[4] = {0, 1, 50, 111};
       for (int rc = 0; rc < 4; ++rc)
@@ -446,52 +416,20 @@ int ImageModel::create(const float* blob, size_t n) {
           }
     }
   }
-  blocks.clear();
-  int cin = 64;
-  for (int li = 0; li < 4; ++li) {
-    const int wd = kLayers[li][0], nb = kLayers[li][1], st = kLayers[li][2];
-    for (int b = 0; b < nb; ++b) {
-      Bottleneck bk;
-      const int s = b == 0 ? st : 1;
-      bk.c1 = conv(wd, cin, 1, 1, 0);
-      bk.c2 = conv(wd, wd, 3, s, 1);
-      bk.c3 = conv(4 * wd, wd, 1, 1, 0);
-      if (b == 0) {
-        bk.has_ds = true;
-        bk.ds = conv(4 * wd, cin, 1, s, 0);
-        // conv3 and the downsample projection as one GEMM over K = [w | cin] (A_DUAL):
-        // bn3(conv3(t)) + bn_ds(conv_ds(x)) = [t | x] . [W3' | Wds']^T + (b3 + bds)
-        bk.c3ds_w_off = w.size();
-        const int K3 = wd, K2 = cin, Kt = wd + cin;
-        w.resize(w.size() + (size_t)4 * wd * Kt);
-        for (int o = 0; o < 4 * wd; ++o) {
-          for (int k = 0; k < K3; ++k) w[bk.c3ds_w_off + (size_t)o * Kt + k] = w[bk.c3.w_off + (size_t)o * K3 + k];
-          for (int k = 0; k < K2; ++k) w[bk.c3ds_w_off + (size_t)o * Kt + K3 + k] = w[bk.ds.w_off + (size_t)o * K2 + k];
-        }
-        bk.c3ds_b_off = pr.size();
-        for (int o = 0; o < 4 * wd; ++o) pr.push_back(pr[bk.c3.b_off + o] + pr[bk.ds.b_off + o]);
-      }
-      blocks.push_back(bk);
-      cin = 4 * wd;
+  // conv3 and the downsample projection of a stage's first block as one GEMM over K = [w | cin] (A_DUAL):
+  // bn3(conv3(t)) + bn_ds(conv_ds(x)) = [t | x] . [W3' | Wds']^T + (b3 + bds)
+  pack_resnet_blocks(rd, w, pr, blocks, [&](Bottleneck& bk, int wd, int cin) {
+    bk.c3ds_w_off = w.size();
+    const int K3 = wd, K2 = cin, Kt = wd + cin;
+    w.resize(w.size() + (size_t)4 * wd * Kt);
+    for (int o = 0; o < 4 * wd; ++o) {
+      for (int k = 0; k < K3; ++k) w[bk.c3ds_w_off + (size_t)o * Kt + k] = w[bk.c3.w_off + (size_t)o * K3 + k];
+      for (int k = 0; k < K2; ++k) w[bk.c3ds_w_off + (size_t)o * Kt + K3 + k] = w[bk.ds.w_off + (size_t)o * K2 + k];
     }
-  }
-  const float* f1w = rd.take((size_t)512 * 2048);
-  const float* f1b = rd.take(512);
-  const float* f2w = rd.take((size_t)7 * 512);
-  const float* f2b = rd.take(7);
-  MEC_REQUIRE(rd.ok && rd.off == n, "image blob size mismatch");
-  fc1_off = pr.size();
-  pr.resize(pr.size() + (size_t)2048 * 512);
-  for (int i = 0; i < 2048; ++i)
-    for (int j = 0; j < 512; ++j) pr[fc1_off + (size_t)i * 512 + j] = f1w[(size_t)j * 2048 + i];
-  fc1b_off = pr.size();
-  pr.insert(pr.end(), f1b, f1b + 512);
-  fc2_off = pr.size();
-  pr.resize(pr.size() + 512 * 7);
-  for (int i = 0; i < 512; ++i)
-    for (int j = 0; j < 7; ++j) pr[fc2_off + (size_t)i * 7 + j] = f2w[(size_t)j * 512 + i];
-  fc2b_off = pr.size();
-  pr.insert(pr.end(), f2b, f2b + 7);
+    bk.c3ds_b_off = pr.size();
+    for (int o = 0; o < 4 * wd; ++o) pr.push_back(pr[bk.c3.b_off + o] + pr[bk.ds.b_off + o]);
+  });
+  MEC_REQUIRE(pack_head(rd, 2048, pr, fc1_off, fc1b_off, fc2_off, fc2b_off), "image blob size mismatch");
   MEC_TRY(upload(wts, w.data(), w.size() * sizeof(f16)));
   MEC_TRY(upload(prm, pr.data(), pr.size() * sizeof(float)));
   return ensure_taps();

@@ -16,13 +16,13 @@
 #include <cmath>
 
 #include "block_ops.h"
+#include "image_pack.h"
 #include "models.h"
 
 namespace mec {
 
 namespace {
 constexpr int STEM_K = 160;  // 3 * 49 = 147 taps, zero-padded to a multiple of 32
-const int kLayers32[4][3] = {{64, 3, 1}, {128, 4, 2}, {256, 6, 2}, {512, 3, 2}};
 }  // namespace
 
 // One thread per 4 consecutive k of one output pixel's im2col row. img: u8 [B,224,224,C]
@@ -363,47 +363,12 @@ int ImageModel::create_f32(const float* blob, size_t n) {
   BlobReader rd(blob, n);
   std::vector<float> w;
   std::vector<float> pr;
-  // BN output estimate (fp32x3 activation planes, activation_exp): max_c |beta_c| + 6 |gamma_c|
-  double est = 0.0;
-  auto bn_fold = [&](int c, std::vector<float>& scale) {
-    const float* g = rd.take(c);
-    const float* b = rd.take(c);
-    const float* rm = rd.take(c);
-    const float* rv = rd.take(c);
-    scale.resize(c);
-    const size_t off = pr.size();
-    est = 0.0;
-    for (int i = 0; i < c; ++i) {
-      const double sc = (double)g[i] / std::sqrt((double)rv[i] + 1e-5);
-      scale[i] = (float)sc;
-      pr.push_back((float)((double)b[i] - (double)rm[i] * sc));
-      est = std::max(est, std::fabs((double)b[i]) + 6.0 * std::fabs((double)g[i]));
-    }
-    return off;
-  };
-  auto conv = [&](int cout, int cin, int ks, int stride, int pad) {
-    ConvLayer L;
-    L.cin = cin; L.cout = cout; L.ks = ks; L.stride = stride; L.pad = pad;
-    const float* src = rd.take((size_t)cout * cin * ks * ks);
-    std::vector<float> scale;
-    L.b_off = bn_fold(cout, scale);
-    L.x3_est = est;
-    L.w_off = w.size();
-    w.resize(w.size() + (size_t)cout * cin * ks * ks);
-    if (!rd.ok) return L;
-    for (int o = 0; o < cout; ++o)
-      for (int kh = 0; kh < ks; ++kh)
-        for (int kw = 0; kw < ks; ++kw)
-          for (int c = 0; c < cin; ++c)
-            w[L.w_off + (((size_t)o * ks + kh) * ks + kw) * cin + c] =
-                (float)((double)src[(((size_t)o * cin + c) * ks + kh) * ks + kw] * scale[o]);
-    return L;
-  };
   {  // stem: [64][160], k = c*49 + kh*7 + kw (torch [64][3][7][7] order), BN scale folded
     const float* src = rd.take((size_t)64 * 3 * 49);
-    std::vector<float> scale;
-    stem.b_off = bn_fold(64, scale);
-    stem.x3_est = est;
+    const BnFold bn = bn_fold(rd, 64);
+    std::vector<float> scale(bn.scale.begin(), bn.scale.end());  // rounded to float first, as pack_conv
+    stem.b_off = append_shift(pr, bn);
+    stem.x3_est = bn.est;
     stem.cin = 3; stem.cout = 64; stem.ks = 7; stem.stride = 2; stem.pad = 3;
     stem.w_off = w.size();
     w.resize(w.size() + (size_t)64 * STEM_K, 0.f);
@@ -427,41 +392,8 @@ int ImageModel::create_f32(const float* blob, size_t n) {
           w[stem_gray32_off + ((size_t)t * 2 + 1) * 64 + o] = (float)m;
         }
   }
-  blocks.clear();
-  int cin = 64;
-  for (int li = 0; li < 4; ++li) {
-    const int wd = kLayers32[li][0], nb = kLayers32[li][1], st = kLayers32[li][2];
-    for (int b = 0; b < nb; ++b) {
-      Bottleneck bk;
-      const int s = b == 0 ? st : 1;
-      bk.c1 = conv(wd, cin, 1, 1, 0);
-      bk.c2 = conv(wd, wd, 3, s, 1);
-      bk.c3 = conv(4 * wd, wd, 1, 1, 0);
-      if (b == 0) {
-        bk.has_ds = true;
-        bk.ds = conv(4 * wd, cin, 1, s, 0);
-      }
-      blocks.push_back(bk);
-      cin = 4 * wd;
-    }
-  }
-  const float* f1w = rd.take((size_t)512 * 2048);
-  const float* f1b = rd.take(512);
-  const float* f2w = rd.take((size_t)7 * 512);
-  const float* f2b = rd.take(7);
-  MEC_REQUIRE(rd.ok && rd.off == n, "image blob size mismatch");
-  fc1_off = pr.size();
-  pr.resize(pr.size() + (size_t)2048 * 512);
-  for (int i = 0; i < 2048; ++i)
-    for (int j = 0; j < 512; ++j) pr[fc1_off + (size_t)i * 512 + j] = f1w[(size_t)j * 2048 + i];
-  fc1b_off = pr.size();
-  pr.insert(pr.end(), f1b, f1b + 512);
-  fc2_off = pr.size();
-  pr.resize(pr.size() + 512 * 7);
-  for (int i = 0; i < 512; ++i)
-    for (int j = 0; j < 7; ++j) pr[fc2_off + (size_t)i * 7 + j] = f2w[(size_t)j * 512 + i];
-  fc2b_off = pr.size();
-  pr.insert(pr.end(), f2b, f2b + 7);
+  pack_resnet_blocks(rd, w, pr, blocks, [](Bottleneck&, int, int) {});  // image_pack.h
+  MEC_REQUIRE(pack_head(rd, 2048, pr, fc1_off, fc1b_off, fc2_off, fc2b_off), "image blob size mismatch");
   MEC_TRY(upload(wts32, w.data(), w.size() * sizeof(float)));
   MEC_TRY(upload(prm, pr.data(), pr.size() * sizeof(float)));
   if (prec == PREC_FP32X3) {
@@ -480,19 +412,14 @@ int ImageModel::create_f32(const float* blob, size_t n) {
       stem_x3_up = std::ldexp(1.0f, e);
       stem.x3_scale = std::ldexp(1.0f, -e);
     }
-    // Activation-plane scales (activation_exp, BN estimates): the stem output, each block's conv1 /
+    // Activation-plane scales (x3_exp, BN estimates): the stem output, each block's conv1 /
     // conv2 outputs, and one scale per stage for the residual stream (a block's output and its
     // identity input share it). A conv's planes then carry y 2^s_out for input planes x 2^s_in: its
     // epilogue scale becomes 2^-e 2^(s_out - s_in) and its BN shift b 2^s_out (ReLU and the residual
     // add commute with the power of two: the f32 values are the unscaled ones times 2^s_out exactly).
     // The downsample of a stage's first block reads the block input (s_in) beside conv3's T2 (s_t2)
     // in one dual GEMM: its weights are pre-scaled by 2^(s_t2 - s_in) so both halves of K carry 2^s_t2.
-    // opts.x3_plane_scale 0: every exponent 0 (the unscaled planes, A/B only)
-    // opts.x3_headroom: 2^-x3_headroom of the target (a handle re-created after a range trip)
-    auto aexp = [&](double b, double t) {
-      return opts.x3_plane_scale ? activation_exp(b, std::ldexp(t, -opts.x3_headroom)) : 0;
-    };
-    stem.x3_s = aexp(stem.x3_est, kX3EstimateTarget);
+    stem.x3_s = x3_exp(stem.x3_est, kX3EstimateTarget);
     x3_note("stem", stem.x3_s, stem.x3_est);
     {
       int s_prev = stem.x3_s;
@@ -507,13 +434,13 @@ int ImageModel::create_f32(const float* blob, size_t n) {
           e_stream = bk.c3.x3_est + (bk.has_ds ? bk.ds.x3_est : e_stream);
           e_max = std::max(e_max, e_stream);
         }
-        const int s_stage = aexp(e_max, kX3EstimateTarget);
+        const int s_stage = x3_exp(e_max, kX3EstimateTarget);
         const std::string st = "layer" + std::to_string(stage + 1);
         x3_note(st + ".out", s_stage, e_max);
         for (size_t bi = b0; bi < b1; ++bi) {
           Bottleneck& bk = blocks[bi];
-          bk.c1.x3_s = aexp(bk.c1.x3_est, kX3EstimateTarget);
-          bk.c2.x3_s = aexp(bk.c2.x3_est, kX3EstimateTarget);
+          bk.c1.x3_s = x3_exp(bk.c1.x3_est, kX3EstimateTarget);
+          bk.c2.x3_s = x3_exp(bk.c2.x3_est, kX3EstimateTarget);
           bk.c3.x3_s = s_stage;
           bk.x3_s_in = bi == b0 ? s_prev : s_stage;
           const std::string bn = st + "." + std::to_string(bi - b0);

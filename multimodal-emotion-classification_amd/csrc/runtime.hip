@@ -138,6 +138,10 @@ void Model::x3_note(const std::string& name, int s, double bound) {
   x3_report += buf;
 }
 
+int Model::x3_exp(double bound, double target) const {
+  return opts.x3_plane_scale ? activation_exp(bound, std::ldexp(target, -opts.x3_headroom)) : 0;
+}
+
 float split_planes(const float* w, size_t n, f16* hi, f16* lo) {
   float mx = 0.f;
   for (size_t i = 0; i < n; ++i) mx = std::max(mx, std::fabs(w[i]));

@@ -36,6 +36,9 @@ def main():
                                    'with MEC_LIB naming the other build)')
     ap.add_argument('--handles', default='', help="pipeline only: the handles that get --opt, e.g. 'text' "
                                                   "(default: every handle)")
+    ap.add_argument('--input', default='gray48', choices=['gray48', 'gray224', 'rgb224'],
+                    help='image / image_mbv2: the input form (each has its own stem weight table); the 224 forms '
+                         'go through forward_u8')
     ap.add_argument('--set', action='append', default=[], metavar='KEY=VALUE',
                     help='process-default option set before the handles are created (creation-time knobs such '
                          'as x3_plane_scale)')
@@ -62,7 +65,13 @@ def main():
     else:
         m = (engine.ImageEncoder(device=dev, precision=a.precision) if a.enc == 'image'
              else engine.MobileNetImageEncoder(device=dev, precision=a.precision))
-        args = (engine.to_device(syn.image_inputs(a.batch, seed=0), dev),)
+        if a.input == 'gray48':
+            args = (engine.to_device(syn.image_inputs(a.batch, seed=0), dev),)
+        else:
+            g = torch.Generator().manual_seed(0)
+            args = (torch.randint(0, 256, (a.batch, 224, 224, 1 if a.input == 'gray224' else 3), generator=g,
+                                  dtype=torch.uint8).to(dev),)
+            m.forward = m.forward_u8
     outs, times = {}, {v: [] for v in a.values}
     def fwd():
         r = m.forward(*args)
@@ -95,7 +104,9 @@ def main():
     base = outs[a.values[0]]
     if a.save:
         import numpy as np
-        np.savez(a.save, *[t.cpu().numpy() for t in base])
+        # the fp32x3 handles' exponent report rides along, so a cross-build comparison covers it
+        report = m.x3_report() if a.precision == 'fp32x3' and hasattr(m, 'x3_report') else ''
+        np.savez(a.save, *[t.cpu().numpy() for t in base], x3_report=np.array(report))
     for v in a.values:
         d = [float((x - y).abs().max()) for x, y in zip(outs[v], base)]
         print(json.dumps({'enc': a.enc, 'precision': a.precision, a.opt: v, 'ms': round(sorted(times[v])[len(times[v]) // 2], 4),
