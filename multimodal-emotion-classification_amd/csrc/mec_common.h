@@ -95,8 +95,14 @@ struct Options {
   int conv3x3_direct = 1;   // ResNet layer1 conv2 on the halo-tile kernel (conv3x3.hip)
   int conv3x3_halo = 1;     // layers 2-3 stride-1 conv2 on the halo kernel (conv3x3_halo.hip)
   int stem_gray_f32 = 1;    // fp32 gray stem as one conv + pool kernel (else im2col + GEMM + pool)
+  // Images per ResNet50 layer1-2 pass, f16 and fp32x3 (0 = whole batch; image_model.h resnet_blocks). Measured
+  // at B = 256 (tools/encoder_profile.py --opt resnet_chunk=N): 0 -> 4.23-4.25 ms, 128 -> 4.38, 64 -> 4.44-4.49,
+  // 32 -> 5.08: the smaller GEMMs lose more than the cache residency gains, so chunking is off.
   int resnet_chunk = 0;
-  int pw_chain = 2;         // layer1 seam kernels (pw_chain.hip)
+  // layer1 seam kernels (pw_chain.hip): 0 off, 1 the 256 -> 64 seams (block 1 -> 2, 2 -> 3), 2 also the
+  // 256 -> 128 seam into layer2 (block 3 -> layer2 block 1). Image encoder at B = 256 (tools/ab_option.py, one
+  // process): 4.03 / 3.83 / 3.75 ms for 0 / 1 / 2.
+  int pw_chain = 2;
   int pw_chain_form = 0;
   // fp32x3 layer1 seam kernels (pw_chain_x3.hip): 0 off, 1 the 256 -> 64 seams (block 1 -> 2 with
   // the downsample, 2 -> 3), 2 also the 256 -> 128 seam into layer2

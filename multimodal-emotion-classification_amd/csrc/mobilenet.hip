@@ -21,6 +21,7 @@
 #include <cmath>
 
 #include "block_ops.h"
+#include "image_model.h"
 #include "image_pack.h"
 #include "models.h"
 
@@ -806,125 +807,83 @@ __global__ __launch_bounds__(256) void mbv2_pad_f16_kernel(const f16* __restrict
       c < cin ? *reinterpret_cast<const half8*>(x + r * cin + c) : half8{0, 0, 0, 0, 0, 0, 0, 0};
 }
 
+// f16 policy of the layered blocks (image_model.h): f16 rows of lcinp / lcoutp channels, the layered matrices
+struct MbF16 {
+  using IO = f16;
+  static constexpr bool kLayered = true;
+  const MobileNetModel& m;
+  const f16* Wt;
+  const float* P;
+  Prof& prof;
+  hipStream_t s;
+  f16 *E, *D, *L;
+  void expand(GemmParams& g, const MbBlock& b, size_t, const f16* in) const {
+    g.A = in; g.B = Wt + b.lwe_off; g.bias = P + b.be_off; g.C16 = E;
+  }
+  int depthwise(const MbBlock& b, int B, int h, int oh, const f16*) const {
+    const size_t items = (size_t)B * oh * (b.hidp / 8);  // one output row of one 8-channel group each
+    hipLaunchKernelGGL(b.stride == 2 ? mbv2_dw_f16_kernel<2> : mbv2_dw_f16_kernel<1>, dim3((unsigned)((items + 255) / 256)),
+                       dim3(256), 0, s, E, h, oh, b.hidp, P + b.wd_off, P + b.bd_off, D, items);
+    MEC_LAUNCH_CHECK();
+    return 0;
+  }
+  void project(GemmParams& g, const MbBlock& b, size_t, const f16* res, f16* out) const {
+    g.A = D; g.B = Wt + b.lwp_off; g.bias = P + b.lbp_off; g.C16 = out; g.R = res;
+  }
+  void last(GemmParams& g, const f16* in) const { g.A = in; g.B = Wt + m.last_w_off; g.bias = P + m.last_b_off; g.C16 = L; }
+  int launch(const GemmParams& g, Prof* pr, int tag) const { return launch_gemm(g, s, pr, tag); }
+  // the fused blocks' rows -> the layered row stride
+  int enter(const MbBlock& b, int B, int h, const void* x, f16*, f16* P1, const f16*& in) const {
+    in = static_cast<const f16*>(x);
+    if (b.cin == b.lcinp) return 0;
+    const size_t rows = (size_t)B * h * h, items = rows * (b.lcinp / 8);
+    hipLaunchKernelGGL(mbv2_pad_f16_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, in, rows, b.cin,
+                       b.lcinp, P1);
+    MEC_LAUNCH_CHECK();
+    in = P1;
+    return 0;
+  }
+};
+
 int MobileNetModel::forward_u8(const uint8_t* img, int B, int H, int W, int C, float* feat, float* logits,
                                float* probs, hipStream_t s) {
-  MEC_REQUIRE(B >= 0, "image: B < 0");
-  if (B == 0) return 0;
-  MEC_REQUIRE(img && feat && logits && probs, "image: null pointer");
-  const bool fer = (H == 48 && W == 48 && C == 1);
-  MEC_REQUIRE(fer || (H == 224 && W == 224 && (C == 1 || C == 3)),
-              "image: input must be u8 [B,48,48,1] (GPU resize) or [B,224,224,{1,3}] (already resized)");
+  if (const int r = image_args(img, B, H, W, C, feat, logits, probs)) return std::min(r, 0);
   if (prec == PREC_FP32) return forward_f32(img, B, H, W, C, feat, logits, probs, s);
   if (prec == PREC_FP32X3) return forward_x3(img, B, H, W, C, feat, logits, probs, s);
-  // layered tail: blocks[l0 ..] (features[l0 + 1 ..]) as expand GEMM -> depthwise -> project GEMM
-  size_t l0 = blocks.size();
-  if (opt().mbv2_layered16) {
-    l0 = (size_t)opt().mbv2_layered16 - 1;
-    for (size_t i = l0; i < blocks.size(); ++i)
-      MEC_REQUIRE(blocks[i].lwe_off, "mbv2: mbv2_layered16 names a block without a layered form");
-  }
-  size_t pe = 0, pd = 0, pp = 0;  // per-image elements of E, D and the tail's block I/O rows
-  {
-    int hh = 112;
-    for (size_t i = 0; i < blocks.size(); ++i) {
-      const MbBlock& b = blocks[i];
-      const int oh = b.stride == 2 ? hh / 2 : hh;
-      if (i >= l0) {
-        pe = std::max(pe, (size_t)hh * hh * b.hidp);
-        pd = std::max(pd, (size_t)oh * oh * b.hidp);
-        pp = std::max(pp, std::max((size_t)hh * hh * b.lcinp, (size_t)oh * oh * b.lcoutp));
-      }
-      hh = oh;
-    }
-  }
-  const size_t per_big = (size_t)112 * 112 * 16;  // largest block output (features[1]), elements
-  const size_t per_last = (size_t)49 * 1280;
+  size_t l0, pe, pd, pp;
+  MEC_TRY(mb_layered_from(blocks, opt().mbv2_layered16, false, "mbv2: mbv2_layered16 names a block without a layered form", l0));
+  mb_tail_sizes<true>(blocks, l0, pe, pd, pp);
   uint8_t* resized;
   f16 *X, *Y, *L, *Eb, *Db, *P0, *P1;
   float* pooled;
   MEC_TRY(carve(ws, [&](Carver& c) {
-    resized = c.take<uint8_t>((size_t)B * 224 * 224);
-    X = c.take<f16>(B * per_big);
-    Y = c.take<f16>(B * per_big);
-    L = c.take<f16>(B * per_last);
-    pooled = c.take<float>((size_t)B * 1280);
+    resized = c.take<uint8_t>(B * kImgPixels);
+    X = c.take<f16>(B * kMbBig);
+    Y = c.take<f16>(B * kMbBig);
+    L = c.take<f16>(B * kMbLast);
+    pooled = c.take<float>((size_t)B * kMbFeat);
     Eb = c.take<f16>(B * pe);
     Db = c.take<f16>(B * pd);
     P0 = c.take<f16>(B * pp);
     P1 = c.take<f16>(B * pp);
   }));
-
-  const f16* Wt = wts.as<f16>();
-  const float* P = prm.as<float>();
-  const uint8_t* stem_in = img;
-  if (fer) {
-    MEC_TRY(resize_u8(img, B, 48, 48, resized, 224, 224, s));
-    stem_in = resized;
-  }
+  MbF16 p{*this, wts.as<f16>(), prm.as<float>(), prof, s, Eb, Db, L};
+  StemIn in;
+  MEC_TRY(image_stem_input(img, B, H, W, C, resized, s, in));
   MEC_TRY(prof.begin(TAG_MBV2_BLOCK, s));
-  const f16* cur = reinterpret_cast<const f16*>(stem_in);
-  f16* out = X;
-  int h = 112;
-  for (size_t i = 0; i < blocks.size(); ++i) {
-    const MbBlock& b = blocks[i];
-    if (i >= l0) {
-      const int oh = b.stride == 2 ? h / 2 : h;
-      const f16* in = cur;
-      f16* pout = (cur == P0) ? P1 : P0;
-      if (i == l0 && b.cin != b.lcinp) {  // the fused blocks' rows -> the layered row stride
-        const size_t rows = (size_t)B * h * h, items = rows * (b.lcinp / 8);
-        hipLaunchKernelGGL(mbv2_pad_f16_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, cur, rows,
-                           b.cin, b.lcinp, P1);
-        MEC_LAUNCH_CHECK();
-        in = P1;
-        pout = P0;
-      }
-      GemmParams g;  // expand + BN + ReLU6 -> E f16
-      g.A = in; g.B = Wt + b.lwe_off; g.bias = P + b.be_off; g.act = ACT_RELU6; g.C16 = Eb;
-      g.M = B * h * h; g.N = b.hidp; g.K = b.lcinp;
-      MEC_TRY(launch_gemm(g, s, nullptr, 0));  // inside the TAG_MBV2_BLOCK window
-      const size_t items = (size_t)B * oh * (b.hidp / 8);  // one output row of one 8-channel group each
-      if (b.stride == 2)
-        hipLaunchKernelGGL(mbv2_dw_f16_kernel<2>, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, Eb, h, oh,
-                           b.hidp, P + b.wd_off, P + b.bd_off, Db, items);
-      else
-        hipLaunchKernelGGL(mbv2_dw_f16_kernel<1>, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, Eb, h, oh,
-                           b.hidp, P + b.wd_off, P + b.bd_off, Db, items);
-      MEC_LAUNCH_CHECK();
-      g = GemmParams();  // project + BN (+ the block input) -> f16 rows of lcoutp channels
-      g.A = Db; g.B = Wt + b.lwp_off; g.bias = P + b.lbp_off; g.act = ACT_NONE; g.C16 = pout;
-      if (b.stride == 1 && b.cin == b.cout) g.R = in;
-      g.M = B * oh * oh; g.N = b.lcoutp; g.K = b.hidp;
-      MEC_TRY(launch_gemm(g, s, nullptr, 0));
-      cur = pout;
-      h = oh;
-      continue;
-    }
+  const f16* last;
+  int h;
+  MEC_TRY(mb_walk(blocks, l0, p, B, in.img, X, Y, P0, P1, [&](size_t i, const MbBlock& b, const void* x, f16* y, int hh) {
     MbArgs a;
-    a.x = cur; a.y = out; a.H = h; a.OH = b.stride == 2 ? h / 2 : h;
-    a.cin = b.cin; a.cout = b.cout; a.hidp = b.hidp;
-    a.We = Wt + b.we_off; a.be = P + b.be_off; a.Wd = P + b.wd_off; a.bd = P + b.bd_off;
-    a.Wp = Wt + b.wp_off; a.bp = P + b.bp_off;
-    a.stem_w = P + (C == 3 ? stem_rgb_off : stem_w_off);
-    a.stem_corr = P + stem_corr_off;
-    MEC_TRY(dispatch_block(b, a, B, i == 0 ? (C == 3 ? 3 : 1) : 0, s));
-    cur = out;
-    out = (out == X) ? Y : X;
-    h = a.OH;
-  }
+    mb_fused_args(a, *this, b, x, y, hh, C);
+    a.hidp = b.hidp;
+    return dispatch_block(b, a, B, i == 0 ? (C == 3 ? 3 : 1) : 0, s);
+  }, last, h));
   MEC_TRY(prof.end(TAG_MBV2_BLOCK, s));
-  {  // features[18] 1x1 320 -> 1280 + BN + ReLU6
-    GemmParams g;
-    g.A = cur; g.B = Wt + last_w_off; g.bias = P + last_b_off; g.act = ACT_RELU6; g.C16 = L;
-    g.M = B * h * h; g.N = 1280; g.K = 320;
-    MEC_TRY(launch_gemm(g, s, &prof, TAG_MBV2_LAST));
-  }
-  hipLaunchKernelGGL(avgpool8_kernel, dim3(B), dim3(1280 / 8 * 4), 0, s, L, h * h, 1280, pooled);
+  MEC_TRY(mb_last(p, B, h, last));
+  hipLaunchKernelGGL(avgpool8_kernel, dim3(B), dim3(kMbFeat / 8 * 4), 0, s, L, h * h, kMbFeat, pooled);
   MEC_LAUNCH_CHECK();
-  // classifier[1] Linear(1280,512) + classifier[2] ReLU -> the 512-d feature, then classifier[4] + softmax
-  MEC_TRY(launch_linear_mfma<BACT_RELU>(pooled, 1280, B, 1280, P + fc1_off, P + fc1b_off, 512, feat, 512, nullptr, 0, s));
-  MEC_TRY(launch_head7(feat, B, 512, P + fc2_off, P + fc2b_off, logits, probs, s));
-  return 0;
+  return image_outputs(*this, pooled, B, kMbFeat, feat, logits, probs, s);
 }
 
 }  // namespace mec

@@ -16,6 +16,7 @@
 #include <cmath>
 
 #include "block_ops.h"
+#include "image_model.h"
 #include "image_pack.h"
 #include "models.h"
 
@@ -113,92 +114,79 @@ int MobileNetModel::create_f32(const float* blob, size_t n) {
   return 0;
 }
 
+// fp32 policy of a block (image_model.h): f32 rows of cinp / coutp channels (padded to 64), f32 weights on gemm_f32
+struct MbF32 {
+  using IO = float;
+  static constexpr bool kLayered = false;
+  const MobileNetModel& m;
+  const float *Wt, *P;
+  Prof& prof;
+  hipStream_t s;
+  float *E, *D, *L;
+  void expand(GemmParams& g, const MbBlock& b, size_t, const float* in) const {
+    g.A = in; g.B32 = Wt + b.we_off; g.bias = P + b.be_off; g.C32 = E;
+  }
+  int depthwise(const MbBlock& b, int B, int h, int oh, const float* in) const {
+    const size_t total = (size_t)B * oh * oh * (b.hidp / 4);
+    hipLaunchKernelGGL(mbv2_dw_f32_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, b.t != 1 ? E : in, B, h,
+                       b.hidp, b.stride, oh, P + b.wd_off, P + b.bd_off, D);
+    MEC_LAUNCH_CHECK();
+    return 0;
+  }
+  void project(GemmParams& g, const MbBlock& b, size_t, const float* res, float* out) const {
+    g.A = D; g.B32 = Wt + b.wp_off; g.bias = P + b.bp_off; g.C32 = out;
+    if (res) { g.R = res; g.r_f32 = 1; }
+  }
+  void last(GemmParams& g, const float* in) const { g.A = in; g.B32 = Wt + m.last_w_off; g.bias = P + m.last_b_off; g.C32 = L; }
+  int launch(const GemmParams& g, Prof* pr, int tag) const { return launch_gemm_f32(g, s, pr, tag); }
+};
+
 int MobileNetModel::forward_f32(const uint8_t* img, int B, int H, int W, int C, float* feat, float* logits,
                                 float* probs, hipStream_t s) {
   MEC_REQUIRE(wts32.p, "image_mbv2: fp32 weights missing (handle created at f16 precision)");
-  const bool fer = (H == 48 && W == 48 && C == 1);
-  // per image (floats): the largest block input/output, expanded and depthwise tensors
-  size_t big_io = (size_t)112 * 112 * 64, big_e = 0, big_d = 0;
-  {
-    int h = 112;
-    for (const MbBlock& b : blocks) {
-      const int oh = b.stride == 2 ? h / 2 : h;
-      big_e = std::max(big_e, (size_t)h * h * b.hidp);
-      big_d = std::max(big_d, (size_t)oh * oh * b.hidp);
-      big_io = std::max(big_io, (size_t)oh * oh * b.coutp);
-      h = oh;
-    }
-  }
+  // per image (floats): the largest expanded and depthwise tensors and block input/output (block 0's input, the
+  // 112*112*64 stem output, included: a block's cinp is the previous one's coutp)
+  size_t big_io, big_e, big_d;
+  mb_tail_sizes<false>(blocks, 0, big_e, big_d, big_io);
   uint8_t* resized;
   float *A0, *X, *Y, *E, *D, *Lst, *pooled;
   MEC_TRY(carve(ws, [&](Carver& c) {
-    resized = c.take<uint8_t>((size_t)B * 224 * 224);
+    resized = c.take<uint8_t>(B * kImgPixels);
     A0 = c.take<float>((size_t)B * 12544 * MB_STEM_K);
     X = c.take<float>(B * big_io);
     Y = c.take<float>(B * big_io);
     E = c.take<float>(B * big_e);
     D = c.take<float>(B * big_d);
-    Lst = c.take<float>((size_t)B * 49 * 1280);
-    pooled = c.take<float>((size_t)B * 1280);
+    Lst = c.take<float>(B * kMbLast);
+    pooled = c.take<float>((size_t)B * kMbFeat);
   }));
-
-  const float* Wt = wts32.as<float>();
-  const float* P = prm.as<float>();
-  const uint8_t* stem_in = img;
-  int Cin = C;
-  if (fer) {
-    MEC_TRY(resize_u8(img, B, 48, 48, resized, 224, 224, s));
-    stem_in = resized;
-    Cin = 1;
-  }
+  MbF32 p{*this, wts32.as<float>(), prm.as<float>(), prof, s, E, D, Lst};
+  StemIn in;
+  MEC_TRY(image_stem_input(img, B, H, W, C, resized, s, in));
   MEC_TRY(prof.begin(TAG_MBV2_BLOCK, s));
   {
     const size_t total = (size_t)B * 112 * 112 * (MB_STEM_K / 4);
-    hipLaunchKernelGGL(mbv2_stem_im2col_f32_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, stem_in,
-                       B, Cin, A0);
+    hipLaunchKernelGGL(mbv2_stem_im2col_f32_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, in.img,
+                       B, in.C, A0);
     MEC_LAUNCH_CHECK();
   }
   GemmParams g;
-  g.A = A0; g.B32 = Wt + stem_w_off; g.bias = P + stem_corr_off; g.act = ACT_RELU6; g.C32 = X;
+  g.A = A0; g.B32 = p.Wt + stem_w_off; g.bias = p.P + stem_corr_off; g.act = ACT_RELU6; g.C32 = X;
   g.M = B * 112 * 112; g.N = 64; g.K = MB_STEM_K;
   MEC_TRY(launch_gemm_f32(g, s, nullptr, TAG_NONE));
   float* cur = X;
   float* other = Y;
   int h = 112;
-  for (const MbBlock& b : blocks) {
-    const int oh = b.stride == 2 ? h / 2 : h;
-    const float* dw_in = cur;
-    if (b.t != 1) {  // expand 1x1 + BN + ReLU6
-      g = GemmParams();
-      g.A = cur; g.B32 = Wt + b.we_off; g.bias = P + b.be_off; g.act = ACT_RELU6; g.C32 = E;
-      g.M = B * h * h; g.N = b.hidp; g.K = b.cinp;
-      MEC_TRY(launch_gemm_f32(g, s, nullptr, TAG_NONE));
-      dw_in = E;
-    }
-    {
-      const size_t total = (size_t)B * oh * oh * (b.hidp / 4);
-      hipLaunchKernelGGL(mbv2_dw_f32_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, dw_in, B, h,
-                         b.hidp, b.stride, oh, P + b.wd_off, P + b.bd_off, D);
-      MEC_LAUNCH_CHECK();
-    }
-    g = GemmParams();  // project 1x1 + BN (+ residual)
-    g.A = D; g.B32 = Wt + b.wp_off; g.bias = P + b.bp_off; g.C32 = other;
-    if (b.stride == 1 && b.cin == b.cout) { g.R = cur; g.r_f32 = 1; }
-    g.M = B * oh * oh; g.N = b.coutp; g.K = b.hidp;
-    MEC_TRY(launch_gemm_f32(g, s, nullptr, TAG_NONE));
+  for (size_t i = 0; i < blocks.size(); ++i) {
+    MEC_TRY(mb_block(p, blocks[i], i, B, h, cur, other));
     std::swap(cur, other);
-    h = oh;
+    h = mb_out_side(blocks[i], h);
   }
   MEC_TRY(prof.end(TAG_MBV2_BLOCK, s));
-  g = GemmParams();  // features[18] 1x1 320 -> 1280 + BN + ReLU6
-  g.A = cur; g.B32 = Wt + last_w_off; g.bias = P + last_b_off; g.act = ACT_RELU6; g.C32 = Lst;
-  g.M = B * h * h; g.N = 1280; g.K = 320;
-  MEC_TRY(launch_gemm_f32(g, s, &prof, TAG_MBV2_LAST));
-  hipLaunchKernelGGL(avgpool_f32_kernel, dim3(B, 1280 / 256), dim3(256), 0, s, Lst, h * h, 1280, pooled);
+  MEC_TRY(mb_last(p, B, h, cur));
+  hipLaunchKernelGGL(avgpool_f32_kernel, dim3(B, kMbFeat / 256), dim3(256), 0, s, Lst, h * h, kMbFeat, pooled);
   MEC_LAUNCH_CHECK();
-  MEC_TRY(launch_linear_mfma<BACT_RELU>(pooled, 1280, B, 1280, P + fc1_off, P + fc1b_off, 512, feat, 512, nullptr, 0, s));
-  MEC_TRY(launch_head7(feat, B, 512, P + fc2_off, P + fc2b_off, logits, probs, s));
-  return 0;
+  return image_outputs(*this, pooled, B, kMbFeat, feat, logits, probs, s);
 }
 
 }  // namespace mec

@@ -16,6 +16,7 @@
 #include <cmath>
 
 #include "block_ops.h"
+#include "image_model.h"
 #include "image_pack.h"
 #include "models.h"
 
@@ -691,131 +692,96 @@ int MobileNetModel::create_x3(const float* blob, size_t n) {
   return 0;
 }
 
+// fp32x3 policy of the layered blocks (image_model.h): block rows and the depthwise output as hi | lo planes (lo
+// planes plo / dlo halfs after the hi planes), E in f32, the layered matrices' planes with their epilogue scales
+struct MbX3 {
+  using IO = f16;
+  static constexpr bool kLayered = true;
+  const MobileNetModel& m;
+  const f16* Wt;
+  long long wlo, plo, dlo;
+  const float* P;
+  Prof& prof;
+  hipStream_t s;
+  float* E;
+  f16* D;
+  float* L;
+  void expand(GemmParams& g, const MbBlock& b, size_t i, const f16* in) const {  // E = ReLU6(We X 2^-e + be), f32
+    g.split = 1; g.A = in; g.a_lo = plo; g.B = Wt + b.lwe_off; g.b_lo = wlo; g.oscale = m.lx3_scale[2 * i];
+    g.bias = P + b.be_off; g.C32 = E;
+  }
+  int depthwise(const MbBlock& b, int B, int h, int oh, const f16*) const {
+    const size_t items = (size_t)B * oh * (b.hidp / 8);  // one output row of one 8-channel group each
+    hipLaunchKernelGGL(b.stride == 2 ? mbv2_dw_x3_kernel<2> : mbv2_dw_x3_kernel<1>, dim3((unsigned)((items + 255) / 256)),
+                       dim3(256), 0, s, E, h, oh, b.hidp, P + b.wd_off, P + b.bd_off, D, dlo, items);
+    MEC_LAUNCH_CHECK();
+    return 0;
+  }
+  // Y 2^s = Wp D 2^-e 2^(s - 13) + bp 2^s (+ the block input's planes), hi / lo planes
+  void project(GemmParams& g, const MbBlock& b, size_t i, const f16* res, f16* out) const {
+    g.split = 1; g.A = D; g.a_lo = dlo; g.B = Wt + b.lwp_off; g.b_lo = wlo; g.oscale = m.lx3_scale[2 * i + 1];
+    g.bias = P + b.lbp_x3_off; g.C16 = out; g.c_lo = plo;
+    if (res) { g.R = res; g.r_lo = plo; }
+  }
+  void last(GemmParams& g, const f16* in) const {  // the layered tail's planes (320 channels: no padding)
+    g.split = 1; g.A = in; g.a_lo = plo; g.B = Wt + m.last_w_off; g.b_lo = wlo; g.oscale = m.x3_scale.back();
+    g.bias = P + m.last_b_off; g.C32 = L;
+  }
+  int launch(const GemmParams& g, Prof* pr, int tag) const { return launch_gemm(g, s, pr, tag); }
+  // the fused blocks' f32 output -> planes with the layered row stride
+  int enter(const MbBlock& b, int B, int h, const void* x, f16* P0, f16*, const f16*& in) const {
+    const size_t rows = (size_t)B * h * h, items = rows * (b.lcinp / 4);
+    hipLaunchKernelGGL(mbv2_split_pad_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s,
+                       static_cast<const float*>(x), rows, b.cin, b.lcinp, std::ldexp(1.0f, b.x3_s_in), P0, plo,
+                       range_flag());
+    MEC_LAUNCH_CHECK();
+    in = P0;
+    return 0;
+  }
+};
+
 int MobileNetModel::forward_x3(const uint8_t* img, int B, int H, int W, int C, float* feat, float* logits,
                                float* probs, hipStream_t s) {
   MEC_REQUIRE(wts.p && x3_lo && x3_scale.size() == 2 * blocks.size() + 1 && lx3_scale.size() == 2 * blocks.size(),
               "image_mbv2: fp32x3 weights missing");
-  const bool fer = (H == 48 && W == 48 && C == 1);
-  // layered tail: blocks[l0 ..] (features[l0 + 1 ..]) as expand GEMM -> depthwise -> project GEMM
-  // (features[17], 160 -> 320, is layered at every setting: dispatch_x3_block has no fused form of it)
-  size_t l0 = blocks.size() - 1;
-  if (opt().mbv2_layered) l0 = std::min(l0, (size_t)opt().mbv2_layered - 1);
-  for (size_t i = l0; i < blocks.size(); ++i)
-    MEC_REQUIRE(blocks[i].lwe_off, "mbv2 x3: mbv2_layered names a block without a layered form");
-  // per-image element counts of the layered buffers: E (f32), D / block-I/O planes (halfs per plane)
-  size_t pe = 0, pd = 0, pp = 0;
-  {
-    int hh = 112;
-    for (size_t i = 0; i < blocks.size(); ++i) {
-      const MbBlock& b = blocks[i];
-      const int oh = b.stride == 2 ? hh / 2 : hh;
-      if (i >= l0) {
-        pe = std::max(pe, (size_t)hh * hh * b.hidp);
-        pd = std::max(pd, (size_t)oh * oh * b.hidp);
-        pp = std::max(pp, std::max((size_t)hh * hh * b.lcinp, (size_t)oh * oh * b.lcoutp));
-      }
-      hh = oh;
-    }
-  }
-  const size_t per_big = (size_t)112 * 112 * 16;  // largest block output (features[1]), floats
-  const size_t per_last = (size_t)49 * 1280;
+  // features[17], 160 -> 320, is layered at every setting: dispatch_x3_block has no fused form of it
+  size_t l0, pe, pd, pp;  // E in floats, D / block-I/O rows in halfs per plane
+  MEC_TRY(mb_layered_from(blocks, opt().mbv2_layered, true, "mbv2 x3: mbv2_layered names a block without a layered form", l0));
+  mb_tail_sizes<true>(blocks, l0, pe, pd, pp);
   const long long dlo = (long long)B * pd, plo = (long long)B * pp;  // plane offsets (halfs)
   uint8_t* resized;
   float *X, *Y, *Lst, *pooled, *Eb;
   f16 *Db, *P0, *P1;  // hi | lo planes each
   MEC_TRY(carve(ws, [&](Carver& c) {
-    resized = c.take<uint8_t>((size_t)B * 224 * 224);
-    X = c.take<float>(B * per_big);
-    Y = c.take<float>(B * per_big);
-    Lst = c.take<float>(B * per_last);
-    pooled = c.take<float>((size_t)B * 1280);
+    resized = c.take<uint8_t>(B * kImgPixels);
+    X = c.take<float>(B * kMbBig);
+    Y = c.take<float>(B * kMbBig);
+    Lst = c.take<float>(B * kMbLast);
+    pooled = c.take<float>((size_t)B * kMbFeat);
     Eb = c.take<float>(B * pe);
     Db = c.take<f16>(B * pd * 2);
     P0 = c.take<f16>(B * pp * 2);
     P1 = c.take<f16>(B * pp * 2);
   }));
-
-  const f16* Wt = wts.as<f16>();
-  const long long wlo = (long long)x3_lo;
-  const float* P = prm.as<float>();
-  const uint8_t* stem_in = img;
-  if (fer) {
-    MEC_TRY(resize_u8(img, B, 48, 48, resized, 224, 224, s));
-    stem_in = resized;
-  }
+  MbX3 p{*this, wts.as<f16>(), (long long)x3_lo, plo, dlo, prm.as<float>(), prof, s, Eb, Db, Lst};
+  StemIn in;
+  MEC_TRY(image_stem_input(img, B, H, W, C, resized, s, in));
   MEC_TRY(prof.begin(TAG_MBV2_BLOCK, s));
-  const void* cur = stem_in;
-  float* out = X;
-  int h = 112;
-  f16* pin = P0;  // layered blocks: input / output planes
-  for (size_t i = 0; i < blocks.size(); ++i) {
-    const MbBlock& b = blocks[i];
-    if (i >= l0) {
-      const int oh = b.stride == 2 ? h / 2 : h;
-      if (i == l0) {  // the fused blocks' f32 output -> planes with the layered row stride
-        const size_t rows = (size_t)B * h * h, items = rows * (b.lcinp / 4);
-        hipLaunchKernelGGL(mbv2_split_pad_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s,
-                           reinterpret_cast<const float*>(cur), rows, b.cin, b.lcinp, std::ldexp(1.0f, b.x3_s_in), pin,
-                           plo, range_flag());
-        MEC_LAUNCH_CHECK();
-      }
-      f16* pout = pin == P0 ? P1 : P0;
-      GemmParams g;  // expand: E = ReLU6(We X 2^-e + be), f32
-      g.split = 1; g.A = pin; g.a_lo = plo; g.B = Wt + b.lwe_off; g.b_lo = wlo; g.oscale = lx3_scale[2 * i];
-      g.bias = P + b.be_off; g.act = ACT_RELU6; g.C32 = Eb;
-      g.M = B * h * h; g.N = b.hidp; g.K = b.lcinp;
-      MEC_TRY(launch_gemm(g, s, nullptr, 0));  // inside the TAG_MBV2_BLOCK window
-      const size_t items = (size_t)B * oh * (b.hidp / 8);  // one output row of one 8-channel group each
-      if (b.stride == 2)
-        hipLaunchKernelGGL(mbv2_dw_x3_kernel<2>, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, Eb, h, oh,
-                           b.hidp, P + b.wd_off, P + b.bd_off, Db, dlo, items);
-      else
-        hipLaunchKernelGGL(mbv2_dw_x3_kernel<1>, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, Eb, h, oh,
-                           b.hidp, P + b.wd_off, P + b.bd_off, Db, dlo, items);
-      MEC_LAUNCH_CHECK();
-      g = GemmParams();  // project: Y 2^s = Wp D 2^-e 2^(s - 13) + bp 2^s (+ the block input's planes), hi / lo planes
-      g.split = 1; g.A = Db; g.a_lo = dlo; g.B = Wt + b.lwp_off; g.b_lo = wlo; g.oscale = lx3_scale[2 * i + 1];
-      g.bias = P + b.lbp_x3_off; g.act = ACT_NONE; g.C16 = pout; g.c_lo = plo;
-      if (b.stride == 1 && b.cin == b.cout) {
-        g.R = pin;
-        g.r_lo = plo;
-      }
-      g.M = B * oh * oh; g.N = b.lcoutp; g.K = b.hidp;
-      MEC_TRY(launch_gemm(g, s, nullptr, 0));  // inside the TAG_MBV2_BLOCK window
-      pin = pout;
-      h = oh;
-      continue;
-    }
+  const f16* last;
+  int h;
+  MEC_TRY(mb_walk(blocks, l0, p, B, in.img, X, Y, P0, P1, [&](size_t i, const MbBlock& b, const void* x, float* y, int hh) {
     MbX3Args a;
-    a.x = cur; a.y = out; a.H = h; a.OH = b.stride == 2 ? h / 2 : h;
-    a.cin = b.cin; a.cout = b.cout;
-    a.We = Wt + b.we_off; a.we_lo = wlo; a.we_scale = x3_scale[2 * i]; a.x_up = std::ldexp(1.0f, b.x3_s_in);
-    a.be = P + b.be_off; a.Wd = P + b.wd_off; a.bd = P + b.bd_off;
-    a.Wp = Wt + b.wp_off; a.wp_lo = wlo; a.wp_scale = x3_scale[2 * i + 1];
-    a.bp = P + b.bp_off;
-    a.stem_w = P + (C == 3 ? stem_rgb_off : stem_w_off);
-    a.stem_corr = P + stem_corr_off;
+    mb_fused_args(a, *this, b, x, y, hh, C);
+    a.we_lo = p.wlo; a.we_scale = x3_scale[2 * i]; a.x_up = std::ldexp(1.0f, b.x3_s_in);
+    a.wp_lo = p.wlo; a.wp_scale = x3_scale[2 * i + 1];
     a.flag = range_flag();
-    MEC_TRY(dispatch_x3_block(b, a, B, i == 0 ? (C == 3 ? 3 : 1) : 0, s));
-    cur = out;
-    out = (out == X) ? Y : X;
-    h = a.OH;
-  }
+    return dispatch_x3_block(b, a, B, i == 0 ? (C == 3 ? 3 : 1) : 0, s);
+  }, last, h));
   MEC_TRY(prof.end(TAG_MBV2_BLOCK, s));
-  {  // features[18] 1x1 320 -> 1280 + BN + ReLU6 on the split GEMM engine
-    const f16* A = pin;  // the layered tail's planes (320 channels: no padding)
-    const long long llo = plo;
-    GemmParams g;
-    g.split = 1; g.A = A; g.a_lo = llo; g.B = Wt + last_w_off; g.b_lo = wlo; g.oscale = x3_scale.back();
-    g.bias = P + last_b_off; g.act = ACT_RELU6; g.C32 = Lst;
-    g.M = B * h * h; g.N = 1280; g.K = 320;
-    MEC_TRY(launch_gemm(g, s, &prof, TAG_MBV2_LAST));
-  }
-  hipLaunchKernelGGL(avgpool_f32_kernel, dim3(B, 1280 / 256), dim3(256), 0, s, Lst, h * h, 1280, pooled);
+  MEC_TRY(mb_last(p, B, h, last));  // on the split GEMM engine
+  hipLaunchKernelGGL(avgpool_f32_kernel, dim3(B, kMbFeat / 256), dim3(256), 0, s, Lst, h * h, kMbFeat, pooled);
   MEC_LAUNCH_CHECK();
-  MEC_TRY(launch_linear_mfma<BACT_RELU>(pooled, 1280, B, 1280, P + fc1_off, P + fc1b_off, 512, feat, 512, nullptr, 0, s));
-  MEC_TRY(launch_head7(feat, B, 512, P + fc2_off, P + fc2b_off, logits, probs, s));
-  return 0;
+  return image_outputs(*this, pooled, B, kMbFeat, feat, logits, probs, s);
 }
 
 }  // namespace mec

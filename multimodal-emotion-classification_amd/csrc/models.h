@@ -201,6 +201,11 @@ int lstm_seq_f32(const float* xz, const float* U, int B, int L, int units, int r
 
 // ---------------------------------------------------------------- image encoders
 // Both backbones take the same u8 inputs and produce the same (512-d feature, logits, probs).
+// Their six forwards (f16: forward_u8 in resnet.hip / mobilenet.hip; fp32, fp32x3: forward_f32, forward_x3 in
+// resnet_f32.hip / mobilenet_f32.hip / mobilenet_x3.hip) share one shape (image_model.h): the argument check, the
+// workspace carve, the optional 48 -> 224 resize, the precision's own stem, the walk over the backbone's blocks
+// under that precision's policy, the precision's average pool, then the output tail (fc1 + ReLU = the feature,
+// logits, probs).
 struct ImageNet : Model {
   // img u8 [B,H,W,C]: (48,48,1) gray FER2013 (GPU resize), (224,224,1) gray, (224,224,3) RGB
   virtual int forward_u8(const uint8_t* img, int B, int H, int W, int C, float* feat, float* logits, float* probs,
@@ -231,6 +236,9 @@ struct Bottleneck {
   float c3ds_x3_scale = 1.f;              // fp32x3 path: its planes' scale (in wts_dual) and lo offset
   size_t c3ds_x3_lo = 0;
 };
+// The walk (image_model.h resnet_blocks / resnet_walk): per bottleneck conv1 (unless the previous block's seam
+// kernel ran it), conv2, then conv3 + downsample-or-identity + ReLU as GEMMs or, where the policy's block_end
+// takes over, as a seam kernel that also runs the next conv1; layers 1-2 per resnet_chunk images (f16, fp32x3).
 struct ImageModel : ImageNet {
   DevBuf wts;   // f16 conv weights
   DevBuf prm;   // fp32 biases, stem weights, head
@@ -279,6 +287,8 @@ struct MbBlock {
   double x3_est = 0.0;
   size_t lbp_x3_off = 0;
 };
+// The walk (image_model.h mb_walk / mb_block): f16 and fp32x3 run blocks [0, l0) as one fused kernel each and
+// blocks [l0, ..) layered (expand GEMM -> depthwise -> project GEMM); fp32 runs every block layered.
 struct MobileNetModel : ImageNet {
   DevBuf wts;   // f16 1x1 weights
   DevBuf prm;   // fp32 stem, depthwise weights, biases, head

@@ -6,17 +6,11 @@
 #include <cmath>
 
 #include "block_ops.h"
+#include "image_model.h"
 #include "image_pack.h"
 #include "models.h"
 
 namespace mec {
-
-// Images per layer1-2 pass (0 = whole batch). Measured at B = 256 (tools/encoder_profile.py
-// --opt resnet_chunk=N): 0 -> 4.23-4.25 ms, 128 -> 4.38, 64 -> 4.44-4.49, 32 -> 5.08: the
-// smaller GEMMs lose more than the cache residency gains, so chunking is off.
-// layer1 seam kernels (pw_chain.hip): 0 off, 1 the 256 -> 64 seams (block 1 -> 2, 2 -> 3),
-// 2 also the 256 -> 128 seam into layer2 (block 3 -> layer2 block 1). Image encoder at
-// B = 256 (tools/ab_option.py, one process): 4.03 / 3.83 / 3.75 ms for 0 / 1 / 2.
 
 // ----------------------------------------------------------------------------- resize
 // Pillow ImagingResample (bilinear, 8bpc): 22-bit fixed-point taps, horizontal pass into
@@ -435,153 +429,99 @@ int ImageModel::create(const float* blob, size_t n) {
   return ensure_taps();
 }
 
+// f16 policy of the bottleneck walk (image_model.h): f16 NHWC operands, f16 weights with the BN shift as bias,
+// conv3 + downsample as one dual-K GEMM; the layer1 seam kernels (pw_chain.hip) may take over a block's end.
+struct RnF16 {
+  using T = f16;
+  static constexpr bool kDualDs = true, kChunked = true;
+  const f16* Wt;
+  const float* P;
+  Prof& prof;
+  hipStream_t s;
+  f16 *X, *Y, *Xs, *T1, *T2;
+  void a(GemmParams& g, const f16* p) const { g.A = p; }
+  void a2(GemmParams& g, const f16* p) const { g.A2 = p; }
+  void c(GemmParams& g, f16* p) const { g.C16 = p; }
+  void r(GemmParams& g, const f16* p) const { g.R = p; }
+  void w(GemmParams& g, const ConvLayer& L) const { g.B = Wt + L.w_off; g.bias = P + L.b_off; }
+  void w_dual(GemmParams& g, const Bottleneck& bk) const { g.B = Wt + bk.c3ds_w_off; g.bias = P + bk.c3ds_b_off; }
+  int launch(const GemmParams& g, Prof* pr, int tag) const { return launch_gemm(g, s, pr, tag); }
+  int block_end(const RnBlockEnd& e, f16* t2, f16* in, f16* out) const {
+    const Bottleneck &bk = e.bk, *nx = e.nx;
+    if (bk.has_ds && opt().pw_chain && e.wd == 64 && e.st == 1 && e.cin == 64 && e.OH == 56 && nx &&
+        nx->c1.cin == 256 && nx->c1.cout == 64) {
+      // layer1 block 1: conv3 + downsample + ReLU, then block 2's conv1 (pw_chain.hip)
+      MEC_TRY(prof.begin(TAG_RESNET_CONV1X1, s));
+      MEC_TRY(launch_pw_chain_dual(t2, in, Wt + bk.c3ds_w_off, P + bk.c3ds_b_off, Wt + nx->c1.w_off, P + nx->c1.b_off,
+                                   out, T1 + e.pix0 * 64, e.M, s));
+    } else if (!bk.has_ds && opt().pw_chain && e.wd == 64 && e.OH == 56 && nx && nx->c1.cin == 256 &&
+               (nx->c1.cout == 64 || (opt().pw_chain == 2 && nx->c1.cout == 128))) {
+      // conv3 + residual + ReLU, then the next block's conv1 on the rows just produced
+      // (pw_chain.hip): the block output is not read back from HBM. Block 2 -> 3: 186 us
+      // against 164 + 111 us for the two GEMMs; block 3 -> layer2 (N2 = 128) in the
+      // register-weight form (the LDS-weight form, two tile buffers, took 297 us against
+      // 162 + 132).
+      MEC_TRY(prof.begin(TAG_RESNET_CONV1X1, s));
+      MEC_TRY(launch_pw_chain(t2, in, Wt + bk.c3.w_off, P + bk.c3.b_off, Wt + nx->c1.w_off, P + nx->c1.b_off, out,
+                              T1 + e.pix0 * nx->c1.cout, e.M, nx->c1.cout, s));
+    } else {
+      return 0;
+    }
+    MEC_TRY(prof.end(TAG_RESNET_CONV1X1, s));
+    return 1;
+  }
+};
+
 int ImageModel::forward_u8(const uint8_t* img, int B, int H, int W, int C, float* feat, float* logits, float* probs,
                            hipStream_t s) {
-  MEC_REQUIRE(B >= 0, "image: B < 0");
-  if (B == 0) return 0;
-  MEC_REQUIRE(img && feat && logits && probs, "image: null pointer");
-  const bool fer = (H == 48 && W == 48 && C == 1);
-  MEC_REQUIRE(fer || (H == 224 && W == 224 && (C == 1 || C == 3)),
-              "image: input must be u8 [B,48,48,1] (GPU resize) or [B,224,224,{1,3}] (already resized)");
+  if (const int r = image_args(img, B, H, W, C, feat, logits, probs)) return std::min(r, 0);
   if (prec == PREC_FP32) return forward_f32(img, B, H, W, C, feat, logits, probs, s);
   if (prec == PREC_FP32X3) return forward_x3(img, B, H, W, C, feat, logits, probs, s);
-  const size_t per_img_big = (size_t)56 * 56 * 256;  // largest NHWC activation (elements)
-  const size_t per_t1 = (size_t)56 * 56 * 128, per_t2 = (size_t)56 * 56 * 64;
   uint8_t* resized;
   f16 *X, *Y, *T1, *T2;
   float* pooled;  // [B,2048]
   MEC_TRY(carve(ws, [&](Carver& c) {
-    resized = c.take<uint8_t>((size_t)B * 224 * 224);
-    X = c.take<f16>(B * per_img_big);
-    Y = c.take<f16>(B * per_img_big);
-    T1 = c.take<f16>(B * per_t1);
-    T2 = c.take<f16>(B * per_t2);
-    pooled = c.take<float>((size_t)B * 2048);
+    resized = c.take<uint8_t>(B * kImgPixels);
+    X = c.take<f16>(B * kRnBig);
+    Y = c.take<f16>(B * kRnBig);
+    T1 = c.take<f16>(B * kRnT1);
+    T2 = c.take<f16>(B * kRnT2);
+    pooled = c.take<float>((size_t)B * kRnFeat);
   }));
-  // the stem output [B,56,56,64] sits in the last quarter of X: a chunk's layer-1 outputs (4x the
-  // per-image stride) then never reach the stem output of a later chunk's images (resnet_chunk)
-  f16* Xs = X + (size_t)3 * B * 56 * 56 * 64;
-
-  const f16* Wt = wts.as<f16>();
-  const float* P = prm.as<float>();
-  const uint8_t* stem_in = img;
-  if (fer) {
-    MEC_TRY(resize_u8(img, B, 48, 48, resized, 224, 224, s));
-    stem_in = resized;
-  }
-  {  // fused stem conv 7x7/2 + BN + ReLU + maxpool 3x3/2 -> X [B,56,56,64]
+  RnF16 p{wts.as<f16>(), prm.as<float>(), prof, s, X, Y, resnet_stem_slot(X, B), T1, T2};
+  StemIn in;
+  MEC_TRY(image_stem_input(img, B, H, W, C, resized, s, in));
+  {  // fused stem conv 7x7/2 + BN + ReLU + maxpool 3x3/2 -> Xs [B,56,56,64]
     const ConvLayer& st = C == 3 ? stem_rgb : stem;
     MEC_TRY(prof.begin(TAG_RESNET_STEM, s));
     const int ncu = cu_count();
     if (ncu < 0) return -1;
     const int ntiles = B * 49;  // two resident workgroups per CU (VGPR-bound)
     const dim3 sg(std::min(ntiles, 2 * ncu)), sb(256);
-    const f16* sw = Wt + st.w_off;
-    const float *sbias = P + st.b_off, *scorr = P + stem_corr_off;
+    const f16* sw = p.Wt + st.w_off;
+    const float *sbias = p.P + st.b_off, *scorr = p.P + stem_corr_off;
     if (C == 3)
-      hipLaunchKernelGGL(stem_pool_kernel<3>, sg, sb, 0, s, stem_in, ntiles, sw, sbias, scorr, Xs);
+      hipLaunchKernelGGL(stem_pool_kernel<3>, sg, sb, 0, s, in.img, ntiles, sw, sbias, scorr, p.Xs);
 #ifdef MEC_PROBES
     else if (opt().stem_debug == 1)  // probe builds (wrong results): no MFMA / no pool / no prefetch
-      hipLaunchKernelGGL((stem_pool_kernel<1, 1>), sg, sb, 0, s, stem_in, ntiles, sw, sbias, scorr, Xs);
+      hipLaunchKernelGGL((stem_pool_kernel<1, 1>), sg, sb, 0, s, in.img, ntiles, sw, sbias, scorr, p.Xs);
     else if (opt().stem_debug == 2)
-      hipLaunchKernelGGL((stem_pool_kernel<1, 2>), sg, sb, 0, s, stem_in, ntiles, sw, sbias, scorr, Xs);
+      hipLaunchKernelGGL((stem_pool_kernel<1, 2>), sg, sb, 0, s, in.img, ntiles, sw, sbias, scorr, p.Xs);
     else if (opt().stem_debug == 4)
-      hipLaunchKernelGGL((stem_pool_kernel<1, 4>), sg, sb, 0, s, stem_in, ntiles, sw, sbias, scorr, Xs);
+      hipLaunchKernelGGL((stem_pool_kernel<1, 4>), sg, sb, 0, s, in.img, ntiles, sw, sbias, scorr, p.Xs);
     else if (opt().stem_debug == 7)
-      hipLaunchKernelGGL((stem_pool_kernel<1, 7>), sg, sb, 0, s, stem_in, ntiles, sw, sbias, scorr, Xs);
+      hipLaunchKernelGGL((stem_pool_kernel<1, 7>), sg, sb, 0, s, in.img, ntiles, sw, sbias, scorr, p.Xs);
 #endif
     else
-      hipLaunchKernelGGL(stem_pool_kernel<1>, sg, sb, 0, s, stem_in, ntiles, sw, sbias, scorr, Xs);
+      hipLaunchKernelGGL(stem_pool_kernel<1>, sg, sb, 0, s, in.img, ntiles, sw, sbias, scorr, p.Xs);
     MEC_LAUNCH_CHECK();
     MEC_TRY(prof.end(TAG_RESNET_STEM, s));
   }
-  // Bottleneck blocks [b0, b1) over images [i0, i0 + nb) of the batch (NHWC buffers are
-  // image-major, so an image range is a pointer offset). cur/other swap once per block.
-  auto run_blocks = [&](size_t b0, size_t b1, int i0, int nb, int Hin, f16*& cur, f16*& other) -> int {
-    int H = Hin;
-    bool conv1_done = false;  // this block's conv1 already ran in the previous block's seam kernel
-    for (size_t bi = b0; bi < b1; ++bi) {
-      const Bottleneck& bk = blocks[bi];
-      const int wd = bk.c1.cout, cin = bk.c1.cin, st = bk.c2.stride;
-      const int OH = (H + 2 - 3) / st + 1;
-      f16* in = (bi == 0 ? Xs : cur) + (size_t)i0 * H * H * cin;
-      f16* out = other + (size_t)i0 * OH * OH * 4 * wd;
-      f16* t1 = T1 + (size_t)i0 * H * H * wd;
-      f16* t2 = T2 + (size_t)i0 * OH * OH * wd;
-      GemmParams g;
-      if (!conv1_done) {
-        g.A = in; g.B = Wt + bk.c1.w_off; g.bias = P + bk.c1.b_off; g.act = ACT_RELU; g.C16 = t1;
-        g.M = nb * H * H; g.N = wd; g.K = cin;
-        MEC_TRY(launch_gemm(g, s, &prof, TAG_RESNET_CONV1X1));
-      }
-      conv1_done = false;
-      g = GemmParams();
-      g.amode = A_CONV; g.A = t1; g.B = Wt + bk.c2.w_off; g.bias = P + bk.c2.b_off; g.act = ACT_RELU; g.C16 = t2;
-      g.M = nb * OH * OH; g.N = wd; g.K = 9 * wd;
-      g.H = H; g.W = H; g.C = wd; g.OH = OH; g.OW = OH; g.ks = 3; g.stride = st; g.pad = 1;
-      MEC_TRY(launch_gemm(g, s, &prof, TAG_RESNET_CONV3X3));
-      if (bk.has_ds && opt().pw_chain && wd == 64 && st == 1 && cin == 64 && OH == 56 && bi + 1 < b1 &&
-          blocks[bi + 1].c1.cin == 256 && blocks[bi + 1].c1.cout == 64) {
-        // layer1 block 1: conv3 + downsample + ReLU, then block 2's conv1 (pw_chain.hip)
-        const Bottleneck& nx = blocks[bi + 1];
-        MEC_TRY(prof.begin(TAG_RESNET_CONV1X1, s));
-        MEC_TRY(launch_pw_chain_dual(t2, in, Wt + bk.c3ds_w_off, P + bk.c3ds_b_off, Wt + nx.c1.w_off,
-                                     P + nx.c1.b_off, out, T1 + (size_t)i0 * OH * OH * 64, nb * OH * OH, s));
-        MEC_TRY(prof.end(TAG_RESNET_CONV1X1, s));
-        conv1_done = true;
-      } else if (bk.has_ds) {  // conv3 + downsample + add + ReLU in one dual-source GEMM
-        g = GemmParams();
-        g.amode = A_DUAL; g.A = t2; g.K1 = wd; g.A2 = in; g.B = Wt + bk.c3ds_w_off; g.bias = P + bk.c3ds_b_off;
-        g.act = ACT_RELU; g.C16 = out; g.M = nb * OH * OH; g.N = 4 * wd; g.K = wd + cin;
-        g.H = H; g.W = H; g.C = cin; g.OH = OH; g.OW = OH; g.ks = 1; g.stride = st; g.pad = 0;
-        MEC_TRY(launch_gemm(g, s, &prof, TAG_RESNET_CONV1X1));
-      } else if (opt().pw_chain && wd == 64 && OH == 56 && bi + 1 < b1 && blocks[bi + 1].c1.cin == 256 &&
-                 (blocks[bi + 1].c1.cout == 64 || (opt().pw_chain == 2 && blocks[bi + 1].c1.cout == 128))) {
-        // conv3 + residual + ReLU, then the next block's conv1 on the rows just produced
-        // (pw_chain.hip): the block output is not read back from HBM. Block 2 -> 3: 186 us
-        // against 164 + 111 us for the two GEMMs; block 3 -> layer2 (N2 = 128) in the
-        // register-weight form (the LDS-weight form, two tile buffers, took 297 us against
-        // 162 + 132).
-        const Bottleneck& nx = blocks[bi + 1];
-        MEC_TRY(prof.begin(TAG_RESNET_CONV1X1, s));
-        MEC_TRY(launch_pw_chain(t2, in, Wt + bk.c3.w_off, P + bk.c3.b_off, Wt + nx.c1.w_off, P + nx.c1.b_off, out,
-                                T1 + (size_t)i0 * OH * OH * nx.c1.cout, nb * OH * OH, nx.c1.cout, s));
-        MEC_TRY(prof.end(TAG_RESNET_CONV1X1, s));
-        conv1_done = true;
-      } else {
-        g = GemmParams();
-        g.A = t2; g.B = Wt + bk.c3.w_off; g.bias = P + bk.c3.b_off; g.R = in; g.act = ACT_RELU; g.C16 = out;
-        g.M = nb * OH * OH; g.N = 4 * wd; g.K = wd;
-        MEC_TRY(launch_gemm(g, s, &prof, TAG_RESNET_CONV1X1));
-      }
-      std::swap(cur, other);
-      H = OH;
-    }
-    return 0;
-  };
-  // Layers 1-2 can run over chunks of opt().resnet_chunk images, so that a chunk's activations
-  // stay in the 256-MB Infinity Cache between a block's producer and consumer kernels (off by
-  // default: measured slower, see opt().resnet_chunk). Every GEMM row and conv pixel is computed
-  // the same way at any batch split, so the outputs do not depend on the chunk size.
-  constexpr size_t kL12 = 7;  // layer1 (3 blocks) + layer2 (4 blocks)
-  f16* cur = X;
-  f16* other = Y;
-  const int chunk = opt().resnet_chunk > 0 ? std::min(opt().resnet_chunk, B) : B;
-  for (int i0 = 0; i0 < B; i0 += chunk) {
-    f16* c = X;
-    f16* o = Y;
-    MEC_TRY(run_blocks(0, kL12, i0, std::min(chunk, B - i0), 56, c, o));
-    cur = c;
-    other = o;
-  }
-  MEC_TRY(run_blocks(kL12, blocks.size(), 0, B, 28, cur, other));
-  H = 7;
-  hipLaunchKernelGGL(avgpool8_kernel, dim3(B), dim3(2048 / 8 * 4), 0, s, cur, H * H, 2048, pooled);
+  f16* last;
+  MEC_TRY(resnet_blocks(blocks, p, B, last));
+  hipLaunchKernelGGL(avgpool8_kernel, dim3(B), dim3(kRnFeat / 8 * 4), 0, s, last, 7 * 7, kRnFeat, pooled);
   MEC_LAUNCH_CHECK();
-  // fc[1] Linear(2048,512) + fc[2] ReLU -> the 512-d feature (extract_features), then fc[4] + softmax
-  MEC_TRY(launch_linear_mfma<BACT_RELU>(pooled, 2048, B, 2048, P + fc1_off, P + fc1b_off, 512, feat, 512, nullptr, 0, s));
-  MEC_TRY(launch_head7(feat, B, 512, P + fc2_off, P + fc2b_off, logits, probs, s));
-  return 0;
+  return image_outputs(*this, pooled, B, kRnFeat, feat, logits, probs, s);
 }
 
 }  // namespace mec

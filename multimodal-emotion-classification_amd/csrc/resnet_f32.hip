@@ -16,6 +16,7 @@
 #include <cmath>
 
 #include "block_ops.h"
+#include "image_model.h"
 #include "image_pack.h"
 #include "models.h"
 
@@ -526,98 +527,74 @@ __global__ __launch_bounds__(256) void avgpool_split_kernel(const f16* __restric
   y[(size_t)b * C + c] = (s / (float)HW) * down;
 }
 
+// fp32 policy of the bottleneck walk (image_model.h): f32 NHWC operands and weights on gemm_f32, the downsample
+// as its own GEMM into DS, the whole batch at once, no seam kernels.
+struct RnF32 {
+  using T = float;
+  static constexpr bool kDualDs = false, kChunked = false;
+  const float *Wt, *P;
+  Prof& prof;
+  hipStream_t s;
+  float *X, *Y, *Xs, *T1, *T2, *DS;
+  void a(GemmParams& g, const float* p) const { g.A = p; }
+  void c(GemmParams& g, float* p) const { g.C32 = p; }
+  void r(GemmParams& g, const float* p) const { g.R = p; g.r_f32 = 1; }
+  void w(GemmParams& g, const ConvLayer& L) const { g.B32 = Wt + L.w_off; g.bias = P + L.b_off; }
+  int launch(const GemmParams& g, Prof* pr, int tag) const { return launch_gemm_f32(g, s, pr, tag); }
+  int block_end(const RnBlockEnd&, float*, float*, float*) const { return 0; }
+};
+
 int ImageModel::forward_f32(const uint8_t* img, int B, int H, int W, int C, float* feat, float* logits, float* probs,
                             hipStream_t s) {
   MEC_REQUIRE(wts32.p, "image: fp32 weights missing (handle created at f16 precision)");
-  const bool fer = (H == 48 && W == 48 && C == 1);
-  // per image (floats): im2col 12544 x 160; X, Y, DS 56*56*256 (also the 112*112*64 stem
-  // output); T1 56*56*128; T2 56*56*64; pooled 2048
-  const size_t big = (size_t)56 * 56 * 256;
+  // per image (floats): im2col 12544 x 160; X, Y, DS (also the 112*112*64 stem output); T1; T2; pooled
   uint8_t* resized;
   float *A0, *X, *Y, *DS, *T1, *T2, *pooled;
   MEC_TRY(carve(ws, [&](Carver& c) {
-    resized = c.take<uint8_t>((size_t)B * 224 * 224);
+    resized = c.take<uint8_t>(B * kImgPixels);
     A0 = c.take<float>((size_t)B * 12544 * STEM_K);
-    X = c.take<float>(B * big);
-    Y = c.take<float>(B * big);
-    DS = c.take<float>(B * big);
-    T1 = c.take<float>((size_t)B * 56 * 56 * 128);
-    T2 = c.take<float>((size_t)B * 56 * 56 * 64);
-    pooled = c.take<float>((size_t)B * 2048);
+    X = c.take<float>(B * kRnBig);
+    Y = c.take<float>(B * kRnBig);
+    DS = c.take<float>(B * kRnBig);
+    T1 = c.take<float>(B * kRnT1);
+    T2 = c.take<float>(B * kRnT2);
+    pooled = c.take<float>((size_t)B * kRnFeat);
   }));
-
-  const float* Wt = wts32.as<float>();
-  const float* P = prm.as<float>();
-  const uint8_t* stem_in = img;
-  int Cin = C;
-  if (fer) {
-    MEC_TRY(resize_u8(img, B, 48, 48, resized, 224, 224, s));
-    stem_in = resized;
-    Cin = 1;
-  }
+  RnF32 p{wts32.as<float>(), prm.as<float>(), prof, s, X, Y, X, T1, T2, DS};
+  StemIn in;
+  MEC_TRY(image_stem_input(img, B, H, W, C, resized, s, in));
   MEC_TRY(prof.begin(TAG_RESNET_STEM, s));
-  if (Cin == 1 && opt().stem_gray_f32) {  // conv + BN + ReLU + maxpool in one kernel -> X
+  if (in.C == 1 && opt().stem_gray_f32) {  // conv + BN + ReLU + maxpool in one kernel -> X
     const int ncu = cu_count();
     if (ncu < 0) return -1;
     const int ntiles = B * 49;
-    hipLaunchKernelGGL(stem_pool_gray_f32_kernel, dim3(std::min(ntiles, ncu)), dim3(512), 0, s, stem_in, ntiles,
-                       Wt + stem_gray32_off, P + stem.b_off, X);
+    hipLaunchKernelGGL(stem_pool_gray_f32_kernel, dim3(std::min(ntiles, ncu)), dim3(512), 0, s, in.img, ntiles,
+                       p.Wt + stem_gray32_off, p.P + stem.b_off, X);
     MEC_LAUNCH_CHECK();
     MEC_TRY(prof.end(TAG_RESNET_STEM, s));
   } else {
     {
       const size_t total = (size_t)B * 112 * 112 * (STEM_K / 4);
-      hipLaunchKernelGGL(stem_im2col_f32_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, stem_in, B,
-                         Cin, A0);
+      hipLaunchKernelGGL(stem_im2col_f32_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, in.img, B,
+                         in.C, A0);
       MEC_LAUNCH_CHECK();
     }
     MEC_TRY(prof.end(TAG_RESNET_STEM, s));
     GemmParams g;
-    g.A = A0; g.B32 = Wt + stem.w_off; g.bias = P + stem.b_off; g.act = ACT_RELU; g.C32 = Y;
+    g.A = A0; g.B32 = p.Wt + stem.w_off; g.bias = p.P + stem.b_off; g.act = ACT_RELU; g.C32 = Y;
     g.M = B * 112 * 112; g.N = 64; g.K = STEM_K;
     MEC_TRY(launch_gemm_f32(g, s, &prof, TAG_RESNET_STEM));
-    const size_t total = (size_t)B * 56 * 56 * 16;
+    const size_t total = B * kRnStem / 4;
     hipLaunchKernelGGL(maxpool_f32_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, Y, B, 112, 64, 56, X);
     MEC_LAUNCH_CHECK();
   }
-  GemmParams g;
-  float* cur = X;
-  float* other = Y;
-  int Hc = 56;
-  for (const Bottleneck& bk : blocks) {
-    const int wd = bk.c1.cout, cin = bk.c1.cin, st = bk.c2.stride;
-    const int OH = (Hc + 2 - 3) / st + 1;
-    g = GemmParams();
-    g.A = cur; g.B32 = Wt + bk.c1.w_off; g.bias = P + bk.c1.b_off; g.act = ACT_RELU; g.C32 = T1;
-    g.M = B * Hc * Hc; g.N = wd; g.K = cin;
-    MEC_TRY(launch_gemm_f32(g, s, &prof, TAG_RESNET_CONV1X1));
-    g = GemmParams();
-    g.amode = A_CONV; g.A = T1; g.B32 = Wt + bk.c2.w_off; g.bias = P + bk.c2.b_off; g.act = ACT_RELU; g.C32 = T2;
-    g.M = B * OH * OH; g.N = wd; g.K = 9 * wd;
-    g.H = Hc; g.W = Hc; g.C = wd; g.OH = OH; g.OW = OH; g.ks = 3; g.stride = st; g.pad = 1;
-    MEC_TRY(launch_gemm_f32(g, s, &prof, TAG_RESNET_CONV3X3));
-    const float* idn = cur;
-    if (bk.has_ds) {  // downsample = BN(conv1x1/s(x)), no activation
-      g = GemmParams();
-      g.amode = A_CONV; g.A = cur; g.B32 = Wt + bk.ds.w_off; g.bias = P + bk.ds.b_off; g.C32 = DS;
-      g.M = B * OH * OH; g.N = 4 * wd; g.K = cin;
-      g.H = Hc; g.W = Hc; g.C = cin; g.OH = OH; g.OW = OH; g.ks = 1; g.stride = st; g.pad = 0;
-      MEC_TRY(launch_gemm_f32(g, s, &prof, TAG_RESNET_CONV1X1));
-      idn = DS;
-    }
-    g = GemmParams();  // relu(bn3(conv3(t2)) + identity)
-    g.A = T2; g.B32 = Wt + bk.c3.w_off; g.bias = P + bk.c3.b_off; g.R = idn; g.r_f32 = 1; g.act = ACT_RELU;
-    g.C32 = other; g.M = B * OH * OH; g.N = 4 * wd; g.K = wd;
-    MEC_TRY(launch_gemm_f32(g, s, &prof, TAG_RESNET_CONV1X1));
-    std::swap(cur, other);
-    Hc = OH;
-  }
-  hipLaunchKernelGGL(avgpool_f32_kernel, dim3(B, 2048 / 256), dim3(256), 0, s, cur, Hc * Hc, 2048, pooled);
+  float* last;
+  MEC_TRY(resnet_blocks(blocks, p, B, last));
+  hipLaunchKernelGGL(avgpool_f32_kernel, dim3(B, kRnFeat / 256), dim3(256), 0, s, last, 7 * 7, kRnFeat, pooled);
   MEC_LAUNCH_CHECK();
-  MEC_TRY(launch_linear_mfma<BACT_RELU>(pooled, 2048, B, 2048, P + fc1_off, P + fc1b_off, 512, feat, 512, nullptr, 0, s));
-  MEC_TRY(launch_head7(feat, B, 512, P + fc2_off, P + fc2b_off, logits, probs, s));
-  return 0;
+  return image_outputs(*this, pooled, B, kRnFeat, feat, logits, probs, s);
 }
+
 
 // fp32x3 path: the fp32 path with every bottleneck conv on split-f16 operands (gemm_glds.hip
 // split mode: A_PLAIN 1x1 convs, A_CONV 3x3 convs, and each stage's first block's conv3 +
@@ -627,185 +604,122 @@ int ImageModel::forward_f32(const uint8_t* img, int B, int H, int W, int C, floa
 // elements after the hi half, so every operand -- both sources of a dual GEMM included -- finds
 // its lo plane at the same offset; an identity residual is added as hi + lo (exact). The stem
 // (conv + BN + ReLU + max-pool), the average pool and the head are the fp32 path's kernels.
+// Its policy of the bottleneck walk (image_model.h): split operands with their lo planes L after the hi planes,
+// the weights' lo planes at wlo (the dual ones: Wd, at c3ds_x3_lo), each conv's epilogue scale and 2^x3_s bias;
+// the layer1 and layer-2 seam kernels may take over a block's end.
+struct RnX3 {
+  using T = f16;
+  static constexpr bool kDualDs = true, kChunked = true;
+  const f16 *Wt, *Wd;
+  long long wlo, L;
+  const float* P;
+  Prof& prof;
+  hipStream_t s;
+  f16 *X, *Y, *Xs, *T1, *T2;
+  void a(GemmParams& g, const f16* p) const { g.split = 1; g.A = p; g.a_lo = L; }
+  void a2(GemmParams& g, const f16* p) const { g.A2 = p; }
+  void c(GemmParams& g, f16* p) const { g.C16 = p; g.c_lo = L; }
+  void r(GemmParams& g, const f16* p) const { g.R = p; g.r_lo = L; }
+  void w(GemmParams& g, const ConvLayer& c) const {
+    g.B = Wt + c.w_off; g.b_lo = wlo; g.oscale = c.x3_scale; g.bias = P + c.x3b_off;
+  }
+  void w_dual(GemmParams& g, const Bottleneck& bk) const {
+    g.B = Wd + bk.c3ds_w_off; g.b_lo = (long long)bk.c3ds_x3_lo; g.oscale = bk.c3ds_x3_scale; g.bias = P + bk.c3ds_b_off;
+  }
+  int launch(const GemmParams& g, Prof* pr, int tag) const { return launch_gemm(g, s, pr, tag); }
+  int block_end(const RnBlockEnd& e, f16* t2, f16* in, f16* out) const {
+    const Bottleneck& bk = e.bk;
+    // layer1 seams (pw_chain_x3.hip): conv3 (+ downsample or + residual) + ReLU, then the next
+    // block's conv1 on the rows just produced; the block output's planes are not read back
+    const int sx = opt().pw_chain_x3;
+    const Bottleneck* nx = e.nx;
+    const bool seam = sx && nx && e.wd == 64 && e.OH == 56 && nx->c1.cin == 256 &&
+                      (nx->c1.cout == 64 || (sx == 2 && nx->c1.cout == 128)) &&
+                      (!bk.has_ds || (e.st == 1 && e.cin == 64 && nx->c1.cout == 64));
+    // layer-2 seams (pw_seam_x3.hip): conv3 + identity residual + ReLU, then the next block's conv1 (in
+    // layer2, or layer3's first block across the walk's end: pw_seam_x3 2), the block output walked in
+    // 32-channel chunks
+    const int sq = opt().pw_seam_x3;
+    const Bottleneck* nq = e.nxc;
+    const bool seam2 = sq && nq && !bk.has_ds && e.wd == 128 && nq->c1.cin == 512 &&
+                       (nq->c1.cout == 128 || (sq == 2 && nq->c1.cout == 256));
+    if (!seam && !seam2) return 0;
+    GemmParams w3, w1;  // conv3 (with the downsample: the dual matrix) and the next conv1, as the GEMMs take them
+    if (bk.has_ds) w_dual(w3, bk);
+    else w(w3, bk.c3);
+    const ConvLayer& c1 = (seam ? nx : nq)->c1;
+    w(w1, c1);
+    f16* t1 = T1 + e.pix0 * c1.cout;
+    MEC_TRY(prof.begin(TAG_RESNET_CONV1X1, s));
+    if (seam)
+      MEC_TRY(launch_pw_chain_x3(t2, in, L, w3.B, w3.b_lo, w3.oscale, w3.bias, w1.B, w1.b_lo, w1.oscale, w1.bias, out, t1,
+                                 e.M, c1.cout, bk.has_ds, s));
+    else
+      MEC_TRY(launch_pw_seam_x3(t2, in, L, w3.B, w3.b_lo, w3.oscale, w3.bias, w1.B, w1.b_lo, w1.oscale, w1.bias, out, t1,
+                                e.M, e.wd, c1.cout, s));
+    MEC_TRY(prof.end(TAG_RESNET_CONV1X1, s));
+    return 1;
+  }
+};
+
 int ImageModel::forward_x3(const uint8_t* img, int B, int H, int W, int C, float* feat, float* logits, float* probs,
                            hipStream_t s) {
   MEC_REQUIRE(wts.p && wts32.p && wts_dual.p && x3_lo, "image: fp32x3 weights missing");
-  const bool fer = (H == 48 && W == 48 && C == 1);
-  // per image: im2col 12544 x 160 f32 (RGB stem); S32 f32 56*56*64 (stem out; the RGB stem's
-  // 112*112*64 pre-pool map goes to the arena's bytes); arena hi half: X, Y (56*56*256), T1
-  // (56*56*128), T2 (56*56*64) halfs, then the lo half (same layout)
-  const size_t big = (size_t)56 * 56 * 256, t1n = (size_t)56 * 56 * 128, t2n = (size_t)56 * 56 * 64;
-  const size_t arena_img = 2 * big + t1n + t2n;  // halfs per image per half-arena
+  // per image: im2col 12544 x 160 f32 (RGB stem); S32 f32 (stem out; the RGB stem's 112*112*64 pre-pool map goes
+  // to the arena's bytes); arena hi half: X, Y, T1, T2 halfs, then the lo half (same layout)
+  const size_t arena_img = 2 * kRnBig + kRnT1 + kRnT2;  // halfs per image per half-arena
   uint8_t* resized;
   float *A0, *S32, *pooled;
   f16* arena;  // hi half, then lo half
   MEC_TRY(carve(ws, [&](Carver& c) {
-    resized = c.take<uint8_t>((size_t)B * 224 * 224);
+    resized = c.take<uint8_t>(B * kImgPixels);
     A0 = c.take<float>((size_t)B * 12544 * STEM_K);
-    S32 = c.take<float>((size_t)B * 56 * 56 * 64);
-    pooled = c.take<float>((size_t)B * 2048);
+    S32 = c.take<float>(B * kRnStem);
+    pooled = c.take<float>((size_t)B * kRnFeat);
     arena = c.take<f16>(B * arena_img * 2);
   }));
   const long long L = (long long)B * arena_img;  // lo plane = hi plane + L, for every activation
-  f16* X = arena;
-  f16* Y = X + (size_t)B * big;
-  // the stem output [B,56,56,64] sits in the last quarter of X: a chunk's layer-1 outputs (4x the
-  // per-image stride) then never reach the stem output of a later chunk's images (resnet_chunk)
-  f16* Xs = X + (size_t)3 * B * 56 * 56 * 64;
-  f16* T1 = Y + (size_t)B * big;
-  f16* T2 = T1 + (size_t)B * t1n;
-
+  f16 *X = arena, *Y = X + B * kRnBig, *T1 = Y + B * kRnBig, *T2 = T1 + B * kRnT1;
+  RnX3 p{wts.as<f16>(), wts_dual.as<f16>(), (long long)x3_lo, L, prm.as<float>(), prof, s,
+         X, Y, resnet_stem_slot(X, B), T1, T2};
   const float* Wt32 = wts32.as<float>();
-  const f16* Wt = wts.as<f16>();
-  const f16* Wd = wts_dual.as<f16>();
-  const long long wlo = (long long)x3_lo;
-  const float* P = prm.as<float>();
-  const uint8_t* stem_in = img;
-  int Cin = C;
-  if (fer) {
-    MEC_TRY(resize_u8(img, B, 48, 48, resized, 224, 224, s));
-    stem_in = resized;
-    Cin = 1;
-  }
-  // stem -> S32 f32 [B,56,56,64] (the fp32 path's kernels), then split into X's planes
+  StemIn in;
+  MEC_TRY(image_stem_input(img, B, H, W, C, resized, s, in));
+  // stem -> S32 f32 [B,56,56,64] (the fp32 path's kernels), then split into Xs's planes
   MEC_TRY(prof.begin(TAG_RESNET_STEM, s));
-  if (Cin == 1 && opt().stem_gray_f32) {  // conv + BN + ReLU + pool on split weights -> X's planes
+  if (in.C == 1 && opt().stem_gray_f32) {  // conv + BN + ReLU + pool on split weights -> Xs's planes
     const int ncu = cu_count();
     if (ncu < 0) return -1;
     const int ntiles = B * 49;
-    hipLaunchKernelGGL(stem_pool_gray_x3_kernel, dim3(std::min(ntiles, ncu)), dim3(512), 0, s, stem_in, ntiles,
-                       Wt32 + stem_gray32_off, stem_x3_up, std::ldexp(stem.x3_scale, stem.x3_s), P + stem.x3b_off, Xs, L,
-                       range_flag());
+    hipLaunchKernelGGL(stem_pool_gray_x3_kernel, dim3(std::min(ntiles, ncu)), dim3(512), 0, s, in.img, ntiles,
+                       Wt32 + stem_gray32_off, stem_x3_up, std::ldexp(stem.x3_scale, stem.x3_s), p.P + stem.x3b_off, p.Xs,
+                       L, range_flag());
     MEC_LAUNCH_CHECK();
   } else {
     const size_t total = (size_t)B * 112 * 112 * (STEM_K / 4);
-    hipLaunchKernelGGL(stem_im2col_f32_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, stem_in, B,
-                       Cin, A0);
+    hipLaunchKernelGGL(stem_im2col_f32_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, in.img, B,
+                       in.C, A0);
     MEC_LAUNCH_CHECK();
     GemmParams g;  // the 112 x 112 pre-pool map (B * 802816 floats) fits in the arena's bytes
     float* Y32 = reinterpret_cast<float*>(arena);
-    g.A = A0; g.B32 = Wt32 + stem.w_off; g.bias = P + stem.b_off; g.act = ACT_RELU; g.C32 = Y32;
+    g.A = A0; g.B32 = Wt32 + stem.w_off; g.bias = p.P + stem.b_off; g.act = ACT_RELU; g.C32 = Y32;
     g.M = B * 112 * 112; g.N = 64; g.K = STEM_K;
     MEC_TRY(launch_gemm_f32(g, s, nullptr, 0));
-    const size_t tp = (size_t)B * 56 * 56 * 16;
-    hipLaunchKernelGGL(maxpool_f32_kernel, dim3((unsigned)((tp + 255) / 256)), dim3(256), 0, s, Y32, B, 112, 64, 56, S32);
+    const size_t n4 = B * kRnStem / 4;
+    hipLaunchKernelGGL(maxpool_f32_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, Y32, B, 112, 64, 56, S32);
     MEC_LAUNCH_CHECK();
-    const size_t n4 = (size_t)B * 56 * 56 * 64 / 4;
     hipLaunchKernelGGL(split_f32_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, S32, n4,
-                       std::ldexp(1.0f, stem.x3_s), Xs, L, range_flag());
+                       std::ldexp(1.0f, stem.x3_s), p.Xs, L, range_flag());
     MEC_LAUNCH_CHECK();
   }
   MEC_TRY(prof.end(TAG_RESNET_STEM, s));
-  // Bottleneck blocks [b0, b1) over images [i0, i0 + nb) (NHWC planes are image-major: an image range
-  // is a pointer offset; the lo planes stay L elements after their hi planes). cur/other swap per block.
-  // a layer-2 seam into layer3's first block (pw_seam_x3 2) runs that block's conv1 in the previous call
-  bool carry_conv1 = false;
-  auto run_blocks = [&](size_t b0, size_t b1, int i0, int nb, int Hin, f16*& cur, f16*& other, bool cross) -> int {
-    int Hc = Hin;
-    bool conv1_done = carry_conv1;  // this block's conv1 already ran in the previous block's seam kernel
-    carry_conv1 = false;
-    for (size_t bi = b0; bi < b1; ++bi) {
-      const Bottleneck& bk = blocks[bi];
-      const int wd = bk.c1.cout, cin = bk.c1.cin, st = bk.c2.stride;
-      const int OH = (Hc + 2 - 3) / st + 1;
-      f16* in = (bi == 0 ? Xs : cur) + (size_t)i0 * Hc * Hc * cin;
-      f16* out = other + (size_t)i0 * OH * OH * 4 * wd;
-      f16* t1 = T1 + (size_t)i0 * Hc * Hc * wd;
-      f16* t2 = T2 + (size_t)i0 * OH * OH * wd;
-      GemmParams g;
-      if (!conv1_done) {
-        g.split = 1; g.A = in; g.a_lo = L; g.B = Wt + bk.c1.w_off; g.b_lo = wlo; g.oscale = bk.c1.x3_scale;
-        g.bias = P + bk.c1.x3b_off; g.act = ACT_RELU; g.C16 = t1; g.c_lo = L;
-        g.M = nb * Hc * Hc; g.N = wd; g.K = cin;
-        MEC_TRY(launch_gemm(g, s, &prof, TAG_RESNET_CONV1X1));
-      }
-      conv1_done = false;
-      g = GemmParams();
-      g.split = 1; g.amode = A_CONV; g.A = t1; g.a_lo = L; g.B = Wt + bk.c2.w_off; g.b_lo = wlo;
-      g.oscale = bk.c2.x3_scale; g.bias = P + bk.c2.x3b_off; g.act = ACT_RELU; g.C16 = t2; g.c_lo = L;
-      g.M = nb * OH * OH; g.N = wd; g.K = 9 * wd;
-      g.H = Hc; g.W = Hc; g.C = wd; g.OH = OH; g.OW = OH; g.ks = 3; g.stride = st; g.pad = 1;
-      MEC_TRY(launch_gemm(g, s, &prof, TAG_RESNET_CONV3X3));
-      // layer1 seams (pw_chain_x3.hip): conv3 (+ downsample or + residual) + ReLU, then the next
-      // block's conv1 on the rows just produced; the block output's planes are not read back
-      const int sx = opt().pw_chain_x3;
-      const Bottleneck* nx = bi + 1 < b1 ? &blocks[bi + 1] : nullptr;
-      const bool seam = sx && nx && wd == 64 && OH == 56 && nx->c1.cin == 256 &&
-                        (nx->c1.cout == 64 || (sx == 2 && nx->c1.cout == 128)) &&
-                        (!bk.has_ds || (st == 1 && cin == 64 && nx->c1.cout == 64));
-      if (seam) {
-        MEC_TRY(prof.begin(TAG_RESNET_CONV1X1, s));
-        if (bk.has_ds)
-          MEC_TRY(launch_pw_chain_x3(t2, in, L, Wd + bk.c3ds_w_off, (long long)bk.c3ds_x3_lo, bk.c3ds_x3_scale,
-                                     P + bk.c3ds_b_off, Wt + nx->c1.w_off, wlo, nx->c1.x3_scale, P + nx->c1.x3b_off, out,
-                                     T1 + (size_t)i0 * OH * OH * nx->c1.cout, nb * OH * OH, nx->c1.cout, true, s));
-        else
-          MEC_TRY(launch_pw_chain_x3(t2, in, L, Wt + bk.c3.w_off, wlo, bk.c3.x3_scale, P + bk.c3.x3b_off,
-                                     Wt + nx->c1.w_off, wlo, nx->c1.x3_scale, P + nx->c1.x3b_off, out,
-                                     T1 + (size_t)i0 * OH * OH * nx->c1.cout, nb * OH * OH, nx->c1.cout, false, s));
-        MEC_TRY(prof.end(TAG_RESNET_CONV1X1, s));
-        conv1_done = true;
-        std::swap(cur, other);
-        Hc = OH;
-        continue;
-      }
-      // layer-2 seams (pw_seam_x3.hip): conv3 + identity residual + ReLU, then the next block's conv1 (in
-      // layer2, or layer3's first block when `cross`), the block output walked in 32-channel chunks
-      const int sq = opt().pw_seam_x3;
-      const Bottleneck* nq = bi + 1 < b1 ? &blocks[bi + 1] : (cross && bi + 1 < blocks.size() ? &blocks[bi + 1] : nullptr);
-      const bool seam2 = sq && nq && !bk.has_ds && wd == 128 && nq->c1.cin == 512 &&
-                         (nq->c1.cout == 128 || (sq == 2 && nq->c1.cout == 256));
-      if (seam2) {
-        MEC_TRY(prof.begin(TAG_RESNET_CONV1X1, s));
-        MEC_TRY(launch_pw_seam_x3(t2, in, L, Wt + bk.c3.w_off, wlo, bk.c3.x3_scale, P + bk.c3.x3b_off,
-                                  Wt + nq->c1.w_off, wlo, nq->c1.x3_scale, P + nq->c1.x3b_off, out,
-                                  T1 + (size_t)i0 * OH * OH * nq->c1.cout, nb * OH * OH, wd, nq->c1.cout, s));
-        MEC_TRY(prof.end(TAG_RESNET_CONV1X1, s));
-        if (bi + 1 < b1) conv1_done = true;
-        else carry_conv1 = true;
-        std::swap(cur, other);
-        Hc = OH;
-        continue;
-      }
-      g = GemmParams();
-      g.split = 1; g.a_lo = L; g.act = ACT_RELU; g.C16 = out; g.c_lo = L; g.M = nb * OH * OH; g.N = 4 * wd;
-      if (bk.has_ds) {  // relu(bn3(conv3(t2)) + bn_ds(conv_ds/s(x))) as one GEMM over K = [w | cin]
-        g.amode = A_DUAL; g.A = t2; g.K1 = wd; g.A2 = in; g.B = Wd + bk.c3ds_w_off; g.b_lo = (long long)bk.c3ds_x3_lo;
-        g.oscale = bk.c3ds_x3_scale; g.bias = P + bk.c3ds_b_off; g.K = wd + cin;
-        g.H = Hc; g.W = Hc; g.C = cin; g.OH = OH; g.OW = OH; g.ks = 1; g.stride = st; g.pad = 0;
-      } else {  // relu(bn3(conv3(t2)) + x)
-        g.A = t2; g.B = Wt + bk.c3.w_off; g.b_lo = wlo; g.oscale = bk.c3.x3_scale; g.bias = P + bk.c3.x3b_off;
-        g.R = in; g.r_lo = L; g.K = wd;
-      }
-      MEC_TRY(launch_gemm(g, s, &prof, TAG_RESNET_CONV1X1));
-      std::swap(cur, other);
-      Hc = OH;
-    }
-    return 0;
-  };
-  // Layers 1-2 over chunks of opt().resnet_chunk images (0 = the whole batch), so that a chunk's hi /
-  // lo activations can stay in the 256-MB Infinity Cache between a block's producer and consumer
-  // kernels. Every GEMM row and conv pixel is computed the same way at any batch split (every
-  // interleaved split tile sums in one k order), so the outputs do not depend on the chunk size.
-  constexpr size_t kL12 = 7;  // layer1 (3 blocks) + layer2 (4 blocks)
-  f16* cur = X;
-  f16* other = Y;
-  const int chunk = opt().resnet_chunk > 0 ? std::min(opt().resnet_chunk, B) : B;
-  for (int i0 = 0; i0 < B; i0 += chunk) {
-    f16* c = X;
-    f16* o = Y;
-    MEC_TRY(run_blocks(0, kL12, i0, std::min(chunk, B - i0), 56, c, o, chunk == B));
-    cur = c;
-    other = o;
-  }
-  MEC_TRY(run_blocks(kL12, blocks.size(), 0, B, 28, cur, other, false));
-  const int Hc = 7;
-  hipLaunchKernelGGL(avgpool_split_kernel, dim3(B, 2048 / 256), dim3(256), 0, s, cur, L, Hc * Hc, 2048,
+  f16* last;
+  MEC_TRY(resnet_blocks(blocks, p, B, last));
+  hipLaunchKernelGGL(avgpool_split_kernel, dim3(B, kRnFeat / 256), dim3(256), 0, s, last, L, 7 * 7, kRnFeat,
                      std::ldexp(1.0f, -x3_s_out), pooled);
   MEC_LAUNCH_CHECK();
-  MEC_TRY(launch_linear_mfma<BACT_RELU>(pooled, 2048, B, 2048, P + fc1_off, P + fc1b_off, 512, feat, 512, nullptr, 0, s));
-  MEC_TRY(launch_head7(feat, B, 512, P + fc2_off, P + fc2b_off, logits, probs, s));
-  return 0;
+  return image_outputs(*this, pooled, B, kRnFeat, feat, logits, probs, s);
 }
+
 
 }  // namespace mec

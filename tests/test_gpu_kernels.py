@@ -351,6 +351,27 @@ def test_pw_chain_bit_identical(dev, B):
             assert torch.equal(a, b)
 
 
+@pytest.mark.parametrize('chain', [0, 2])
+def test_resnet_f16_chunked_layers_bit_identical(dev, chain):
+    """f16 ResNet50 with layers 1-2 over 2-image chunks of a 5-image batch (chunks of 2, 2 and 1: the
+    smallest batch with a ragged last chunk, so every image-range pointer offset of the block walk is
+    used) against the whole batch at once: identical features, logits and probabilities, with the
+    layer1 seam kernels off (pw_chain 0) and at their default (2)."""
+    from mec import engine, synthetic as syn
+    enc = engine.ImageEncoder(device=dev)
+    gray = engine.to_device(syn.image_inputs(5, seed=91), dev)
+    enc.set_option('pw_chain', chain)
+    outs = []
+    for chunk in (0, 2):
+        enc.set_option('resnet_chunk', chunk)
+        res = enc.forward(gray)
+        torch.cuda.synchronize()
+        outs.append([t.cpu() for t in res])
+    assert len(outs[0]) == 3
+    for a, b in zip(outs[1], outs[0]):
+        assert torch.equal(a, b)
+
+
 @pytest.mark.parametrize('precision', ['f16', 'fp32'])
 def test_bert_layernorm_rows_per_wave_bit_identical(dev, precision):
     """bert_layernorm_kernel<RW> (bert_ln_rows 1 / 2 / 4): each row's arithmetic is the same at
