@@ -192,6 +192,13 @@ int mec_resize_u8(const uint8_t* in, int B, int H, int W, uint8_t* out, int OH, 
 int mec_gemm_f16x3(const void* A, long long a_lo, const void* B, long long b_lo, float oscale, const float* bias,
                    const float* R, void* C16, long long c_lo, float* C32, int M, int N, int K, int act,
                    void* stream);
+/* The same GEMM on paired planes: A is one f16 array [M][2K] and B one [N][2K], K % 32 == 0, each holding
+ * per 32-element K chunk the chunk's hi halfs followed by its lo halfs: element (r, k) of plane p (0 hi,
+ * 1 lo) at r 2K + (k >> 5) 64 + 32 p + (k & 31), so one row's operands of a 32-deep K step are one 128-B
+ * line. C16: with c_paired != 0 one array [M][2N] in the same layout (c_lo unused), else hi / lo planes
+ * c_lo apart as above. Same values as mec_gemm_f16x3 bit for bit (K-interleaved term order only). */
+int mec_gemm_f16x3_paired(const void* A, const void* B, float oscale, const float* bias, const float* R, void* C16,
+                          int c_paired, long long c_lo, float* C32, int M, int N, int K, int act, void* stream);
 int mec_gemm_f16(const void* A, const void* B, const float* bias, const void* R, int r_is_f32, void* C16,
                  float* C32, int M, int N, int K, int act, void* stream);
 /* Implicit-GEMM conv on NHWC f16: x[n,H,W,C], w[Cout][ks][ks][C], y[n,OH,OW,Cout]. */
@@ -316,6 +323,10 @@ int mec_gemm_ex(const mec_gemm_args* a, void* stream);
  *                          narrower envelope, different bits)
  *   "x3_headroom" [0]..24  fp32x3 extra binades of plane headroom, creation-time like x3_plane_scale
  *                          (mec_create_opt above)
+ *   "x3_layout" 0|[1]      fp32x3 text model, creation-time like x3_plane_scale: 1 = weight and activation planes
+ *                          paired ([rows][2K]: per 32-element K chunk the hi halfs, then the lo halfs; see
+ *                          mec_gemm_f16x3_paired), 0 = planar. Same bits. A handle created with gemm_x3_order 0
+ *                          is planar, and a paired handle rejects gemm_x3_order 0
  *   "mbv2_layered" 0|7..17 [8]  fp32x3 MobileNetV2: features[k..17] as expand GEMM -> depthwise -> project GEMM
  *                          (0: every block fused but features[17], layered at every setting)
  *   "mbv2_layered16" 0|7..17 [8]  the same on the f16 path

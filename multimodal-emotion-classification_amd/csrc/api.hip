@@ -345,6 +345,19 @@ int mec_gemm_f16x3(const void* A, long long a_lo, const void* B, long long b_lo,
   })
 }
 
+int mec_gemm_f16x3_paired(const void* A, const void* B, float oscale, const float* bias, const float* R, void* C16,
+                          int c_paired, long long c_lo, float* C32, int M, int N, int K, int act, void* stream) {
+  API_GUARD({
+    MEC_REQUIRE(!C16 || c_paired || c_lo != 0, "mec_gemm_f16x3_paired: a planar C16 needs c_lo");
+    GemmParams g;
+    g.split = 1; g.a_pair = g.b_pair = 1; g.A = A; g.B = reinterpret_cast<const f16*>(B); g.oscale = oscale;
+    g.bias = bias; g.R = R; g.r_f32 = R != nullptr; g.C16 = reinterpret_cast<f16*>(C16);
+    g.c_pair = C16 && c_paired; g.c_lo = C16 && !c_paired ? c_lo : 0;
+    g.C32 = C32; g.M = M; g.N = N; g.K = K; g.act = act;
+    return launch_gemm(g, S(stream), nullptr, TAG_NONE);
+  })
+}
+
 int mec_conv_f16(const void* x, const void* w, const float* bias, const void* R, void* y, int n, int H, int W,
                  int C, int Cout, int ks, int stride, int pad, int act, void* stream) {
   API_GUARD({
@@ -427,6 +440,7 @@ int set_option(Options& o, const std::string& k, int value) {
   if (k == "mbv2_x3_sesw" && (value == 0 || value == 1)) { o.mbv2_x3_sesw = value; return 0; }
   if (k == "x3_plane_scale" && (value == 0 || value == 1)) { o.x3_plane_scale = value; return 0; }
   if (k == "x3_headroom" && value >= 0 && value <= 24) { o.x3_headroom = value; return 0; }
+  if (k == "x3_layout" && (value == 0 || value == 1)) { o.x3_layout = value; return 0; }
   if (k == "qkv_x3_late_dma" && value >= 0 && value <= 2) { o.qkv_x3_late_dma = value; return 0; }
   if (k == "mbv2_layered" && (value == 0 || (value >= 7 && value <= 17))) { o.mbv2_layered = value; return 0; }
   if (k == "mbv2_layered16" && (value == 0 || (value >= 7 && value <= 17))) { o.mbv2_layered16 = value; return 0; }
@@ -495,7 +509,13 @@ int mec_set_option(const char* key, int value) { return set_option(default_optio
 int mec_model_set_option(mec_model* m, const char* key, int value) {
   if (!m || !m->impl) { set_error("null model handle"); return -1; }
   const std::string k = key ? key : "";
-  if (k == "x3_plane_scale" || k == "x3_headroom") {  // read while the weights are packed: too late here
+  if (k == "gemm_x3_order" && value == 0 && m->impl->kind == KIND_TEXT &&
+      static_cast<TextModel*>(m->impl)->x3_paired) {
+    set_error("mec_model_set_option: this text handle's planes are paired (x3_layout 1), which the pass-major term "
+              "order does not read; create it with x3_layout=0 or gemm_x3_order=0");
+    return -1;
+  }
+  if (k == "x3_plane_scale" || k == "x3_headroom" || k == "x3_layout") {  // read while the weights are packed: too late here
     set_error("mec_model_set_option: \"" + k + "\" is a creation-time option (pass it to mec_create_opt, or set "
               "the process default with mec_set_option before mec_create_ex)");
     return -1;

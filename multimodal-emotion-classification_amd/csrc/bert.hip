@@ -77,8 +77,8 @@ __global__ __launch_bounds__(256) void bert_embed_ln_kernel(const int32_t* __res
       const half4 hh = {(f16)u.x, (f16)u.y, (f16)u.z, (f16)u.w};
       const half4 hl = {(f16)(u.x - (float)hh[0]), (f16)(u.y - (float)hh[1]), (f16)(u.z - (float)hh[2]),
                         (f16)(u.w - (float)hh[3])};
-      *reinterpret_cast<half4*>(h16 + (size_t)row * BH + c) = hh;
-      *reinterpret_cast<half4*>(h16 + lo + (size_t)row * BH + c) = hl;
+      *reinterpret_cast<half4*>(h16 + x3_at(lo, row, c, BH, 0)) = hh;  // (lo = kX3Paired: paired planes)
+      *reinterpret_cast<half4*>(h16 + x3_at(lo, row, c, BH, 1)) = hl;
       x3_raise(flag, x3_out_of_range4(u));
     } else if (h16) {  // f16 path (null on the fp32 path)
       const half4 hh = {(f16)o.x, (f16)o.y, (f16)o.z, (f16)o.w};
@@ -146,8 +146,8 @@ __global__ __launch_bounds__(256) void bert_layernorm_kernel(const float* x, int
         const half4 hh = {(f16)u.x, (f16)u.y, (f16)u.z, (f16)u.w};
         const half4 hl = {(f16)(u.x - (float)hh[0]), (f16)(u.y - (float)hh[1]), (f16)(u.z - (float)hh[2]),
                           (f16)(u.w - (float)hh[3])};
-        *reinterpret_cast<half4*>(h16 + (size_t)row * BH + c) = hh;
-        *reinterpret_cast<half4*>(h16 + lo + (size_t)row * BH + c) = hl;
+        *reinterpret_cast<half4*>(h16 + x3_at(lo, row, c, BH, 0)) = hh;  // (lo = kX3Paired: paired planes)
+        *reinterpret_cast<half4*>(h16 + x3_at(lo, row, c, BH, 1)) = hl;
         x3_raise(flag, x3_out_of_range4(u));
       } else if (h16) {  // f16 path (null on the fp32 path)
         const half4 hh = {(f16)o.x, (f16)o.y, (f16)o.z, (f16)o.w};
@@ -535,14 +535,14 @@ __device__ __forceinline__ void attn_head_x3(f16* const (&sK)[2], const f16* con
       *reinterpret_cast<half4*>(sK[1] + rq * BDH + aswz(rq, d >> 3) * 8 + (d & 7)) = lv;
     }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // wave-local rows: no barrier needed
-  f16* out = ctx + (size_t)b * (CLS ? 1 : ATT_L) * BH + h * BDH;
+  const size_t row0 = (size_t)b * (CLS ? 1 : ATT_L);  // (clo = kX3Paired: the context planes are paired)
 #pragma unroll
   for (int pl = 0; pl < 2; ++pl)
 #pragma unroll
     for (int i = 0; i < (CLS ? 1 : 4); ++i) {
       const int c = 64 * i + lane, r = 32 * wave + (c >> 3), kc = c & 7;
       const uint4 v = *reinterpret_cast<const uint4*>(sK[pl] + r * BDH + aswz(r, kc) * 8);
-      if (!CLS || r == 0) *reinterpret_cast<uint4*>(out + (pl ? clo : 0) + (size_t)r * BH + kc * 8) = v;
+      if (!CLS || r == 0) *reinterpret_cast<uint4*>(ctx + x3_at(clo, row0 + r, h * BDH + kc * 8, BH, pl)) = v;
     }
 }
 
@@ -586,34 +586,33 @@ __global__ __launch_bounds__(256, 2) void bert_attention_x3_kernel(const f16* __
   half8 qh[4], ql[4];  // this lane's Q row 32 wave + lr, k chunks 2 kk + lh (the MFMA B operand)
   if constexpr (CLS) {
     const bool own = wave == 0 && lr == 0;
-    const f16* qrow = qc + (size_t)b * BH + h * BDH;
+    // (lo / qclo / clo = kX3Paired: that tensor's planes are paired, x3_at)
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) { qh[kk][j] = (f16)0.f; ql[kk][j] = (f16)0.f; }
       if (own) {
-        qh[kk] = *reinterpret_cast<const half8*>(qrow + (2 * kk + lh) * 8);
-        ql[kk] = *reinterpret_cast<const half8*>(qrow + qclo + (2 * kk + lh) * 8);
+        qh[kk] = *reinterpret_cast<const half8*>(qc + x3_at(qclo, b, h * BDH + (2 * kk + lh) * 8, BH, 0));
+        ql[kk] = *reinterpret_cast<const half8*>(qc + x3_at(qclo, b, h * BDH + (2 * kk + lh) * 8, BH, 1));
       }
     }
   } else {
-    const f16* qrow = qkv + (size_t)b * ATT_L * LD + h * BDH + (size_t)(32 * wave + lr) * LD;
+    const size_t qr = (size_t)b * ATT_L + 32 * wave + lr;
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
-      qh[kk] = *reinterpret_cast<const half8*>(qrow + (2 * kk + lh) * 8);
-      ql[kk] = *reinterpret_cast<const half8*>(qrow + lo + (2 * kk + lh) * 8);
+      qh[kk] = *reinterpret_cast<const half8*>(qkv + x3_at(lo, qr, h * BDH + (2 * kk + lh) * 8, LD, 0));
+      ql[kk] = *reinterpret_cast<const half8*>(qkv + x3_at(lo, qr, h * BDH + (2 * kk + lh) * 8, LD, 1));
     }
   }
 #pragma unroll
   for (int pl = 0; pl < 2; ++pl) {
-    const f16* base = qkv + (pl ? lo : 0) + (size_t)bk * ATT_L * LD + h * BDH;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int c = tid + 256 * i;
       const int row = c >> 3, kc = c & 7;
-      const f16* src = base + (size_t)row * LD + kc * 8;
-      const uint4 k = *reinterpret_cast<const uint4*>(src + KO);
-      const uint4 v = *reinterpret_cast<const uint4*>(src + KO + BH);
+      const size_t kr = (size_t)bk * ATT_L + row;
+      const uint4 k = *reinterpret_cast<const uint4*>(qkv + x3_at(lo, kr, KO + h * BDH + kc * 8, LD, pl));
+      const uint4 v = *reinterpret_cast<const uint4*>(qkv + x3_at(lo, kr, KO + BH + h * BDH + kc * 8, LD, pl));
       *reinterpret_cast<uint4*>(sK[pl] + row * BDH + aswz(row, kc) * 8) = k;
       *reinterpret_cast<uint4*>(sV[pl] + row * BDH + vswz(row, kc) * 8) = v;
     }
@@ -843,7 +842,7 @@ __device__ __forceinline__ int qx_sw(int row, int kc) { return kc ^ ((4 - ((row 
 // stages and 80 KB of LDS in all, so two workgroups share a CU and one's attention phase overlaps the
 // other's GEMM. Both sum every output in the same term and k order: the same bits.
 // PACK: mask = the rows' segment ids (stage_mask), nseq the number of packed rows.
-template <int HP, int PACK = 0>
+template <int HP, int PACK = 0, int PAIR = 0>
 __global__ __launch_bounds__(256 * HP, HP == 1 ? 2 : 1) void bert_qkv_attn_x3_kernel(
     const f16* __restrict__ hs, long long hlo, const f16* __restrict__ wqkv, long long wlo, float oscale,
     const float* __restrict__ bqkv, const int32_t* __restrict__ mask, f16* __restrict__ ctx, long long clo, int nseq,
@@ -880,30 +879,48 @@ __global__ __launch_bounds__(256 * HP, HP == 1 ? 2 : 1) void bert_qkv_attn_x3_ke
 
   // stage loader: LDS row R < 128 = token row R of the sequence; R >= 128 = weight row
   // seg * 768 + (HP hp) * 64 + j for n = R - 128 = seg * 64 HP + j; 16 rows of 64 B per wave-instruction
-  const int lrow = lane >> 2, pch = lane & 3;
-  const f16* src[IT];
-  long long lo_off[IT];
+  // PAIR (hs and wqkv paired, [rows][2 x 768]; hlo / wlo unused): a stage is 128 + QBN rows of 64 halfs, the
+  // K chunk's hi halfs in 16-B chunks 0-3 and its lo halfs in 4-7 (swizzled as the GEMM engine's 128-B rows,
+  // chunk c of row R at c ^ ((R >> 1) & 7)), filled by 8-row x 128-B pieces: whole cache lines, and as many
+  // pieces per wave and stage as the planar form's 16-row x 64-B ones
+  constexpr int NP = PAIR ? 2 * IT : IT;  // source pointers per lane
+  const int lrow = PAIR ? lane >> 3 : lane >> 2, pch = PAIR ? lane & 7 : lane & 3;
+  const f16* src[NP];
+  long long lo_off[PAIR ? 1 : IT];
 #pragma unroll
-  for (int it = 0; it < IT; ++it) {
-    const int R = (it * NW + wave) * 16 + lrow;
-    const int c = qx_sw(R, pch);
+  for (int it = 0; it < NP; ++it) {
+    const int R = (it * NW + wave) * (PAIR ? 8 : 16) + lrow;
+    const int c = PAIR ? pch ^ ((R >> 1) & 7) : qx_sw(R, pch);
+    constexpr int LD = PAIR ? 2 * BH : BH;
     if (R < QA_BM) {
-      src[it] = hs + ((size_t)b * ATT_L + R) * BH + c * 8;
-      lo_off[it] = hlo;
+      src[it] = hs + ((size_t)b * ATT_L + R) * LD + c * 8;
+      if constexpr (!PAIR) lo_off[it] = hlo;
     } else {
       const int n = R - QA_BM, seg = n / (64 * HP), j = n - seg * (64 * HP);
-      src[it] = wqkv + ((size_t)seg * BH + hp * 64 * HP + j) * BH + c * 8;
-      lo_off[it] = wlo;
+      src[it] = wqkv + ((size_t)seg * BH + hp * 64 * HP + j) * LD + c * 8;
+      if constexpr (!PAIR) lo_off[it] = wlo;
     }
   }
   auto issue = [&](int kt, int st) {
     f16* base = smem + st * STAGE;
+    if constexpr (PAIR) {
 #pragma unroll
-    for (int pl = 0; pl < 2; ++pl)
+      for (int it = 0; it < NP; ++it)
+        __builtin_amdgcn_global_load_lds((const void*)(src[it] + kt * 64), (lds_p)(base + (it * NW + wave) * 8 * 64),
+                                         16, 0, 0);
+    } else {
 #pragma unroll
-      for (int it = 0; it < IT; ++it)
-        __builtin_amdgcn_global_load_lds((const void*)(src[it] + (pl ? lo_off[it] : 0) + kt * QX_BK),
-                                         (lds_p)(base + pl * PLANE + (it * NW + wave) * 16 * QX_BK), 16, 0, 0);
+      for (int pl = 0; pl < 2; ++pl)
+#pragma unroll
+        for (int it = 0; it < IT; ++it)
+          __builtin_amdgcn_global_load_lds((const void*)(src[it] + (pl ? lo_off[it] : 0) + kt * QX_BK),
+                                           (lds_p)(base + pl * PLANE + (it * NW + wave) * 16 * QX_BK), 16, 0, 0);
+    }
+  };
+  // fragment of plane pl of stage row r, 16-B k chunk kc
+  auto frag = [&](const f16* sA, int pl, int r, int kc) {
+    if constexpr (PAIR) return *reinterpret_cast<const half8*>(sA + r * 64 + ((4 * pl + kc) ^ ((r >> 1) & 7)) * 8);
+    else return *reinterpret_cast<const half8*>(sA + pl * PLANE + r * QX_BK + qx_sw(r, kc) * 8);
   };
 
   floatx4 acc[4][6];
@@ -927,12 +944,12 @@ __global__ __launch_bounds__(256 * HP, HP == 1 ? 2 : 1) void bert_qkv_attn_x3_ke
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int r = 64 * wm + 16 * i + l16;
-        af[pl][i] = *reinterpret_cast<const half8*>(sA + pl * PLANE + r * QX_BK + qx_sw(r, lq) * 8);
+        af[pl][i] = frag(sA, pl, r, lq);
       }
 #pragma unroll
       for (int j = 0; j < 6; ++j) {
         const int rr = QA_BM + 96 * wn + 16 * j + l16;
-        bf[pl][j] = *reinterpret_cast<const half8*>(sA + pl * PLANE + rr * QX_BK + qx_sw(rr, lq) * 8);
+        bf[pl][j] = frag(sA, pl, rr, lq);
       }
     }
     // the stage is free once every wave holds its fragments: restage it for kt + 2 before the MFMAs
@@ -1036,7 +1053,21 @@ int launch_bert_qkv_attn_x3(const f16* hs, long long hlo, const f16* wqkv, long 
                             const float* bqkv, const int32_t* mask, f16* ctx, long long clo, int B, float qks,
                             hipStream_t s, bool packed) {
   const int one = opt().bert_qkv_attn_x3_heads == 1;
-  if (one && packed)
+  MEC_REQUIRE((hlo == kX3Paired) == (wlo == kX3Paired), "bert_qkv_attn_x3: hs and wqkv are paired together");
+  if (hlo == kX3Paired) {  // paired operand planes (the context planes: clo says which)
+    if (one && packed)
+      hipLaunchKernelGGL((bert_qkv_attn_x3_kernel<1, 1, 1>), dim3(B * 12), dim3(256), 0, s, hs, hlo, wqkv, wlo, oscale,
+                         bqkv, mask, ctx, clo, B, qks, range_flag(), opt().qkv_x3_late_dma);
+    else if (packed)
+      hipLaunchKernelGGL((bert_qkv_attn_x3_kernel<2, 1, 1>), dim3(B * 6), dim3(512), 0, s, hs, hlo, wqkv, wlo, oscale,
+                         bqkv, mask, ctx, clo, B, qks, range_flag(), 0);
+    else if (one)
+      hipLaunchKernelGGL((bert_qkv_attn_x3_kernel<1, 0, 1>), dim3(B * 12), dim3(256), 0, s, hs, hlo, wqkv, wlo, oscale,
+                         bqkv, mask, ctx, clo, B, qks, range_flag(), opt().qkv_x3_late_dma);
+    else
+      hipLaunchKernelGGL((bert_qkv_attn_x3_kernel<2, 0, 1>), dim3(B * 6), dim3(512), 0, s, hs, hlo, wqkv, wlo, oscale,
+                         bqkv, mask, ctx, clo, B, qks, range_flag(), 0);
+  } else if (one && packed)
     hipLaunchKernelGGL((bert_qkv_attn_x3_kernel<1, 1>), dim3(B * 12), dim3(256), 0, s, hs, hlo, wqkv, wlo, oscale, bqkv,
                        mask, ctx, clo, B, qks, range_flag(), opt().qkv_x3_late_dma);
   else if (packed)
@@ -1240,6 +1271,22 @@ int TextModel::create(const float* blob, size_t n) {
       }
     }
     MEC_TRY(upload(x3b, bq.data(), bq.size() * sizeof(float)));
+    x3_paired = opts.x3_layout == 1 && opts.gemm_x3_order == 1;
+    if (x3_paired) {  // the same planes, each matrix [N][K] paired at twice its planar offset
+      std::vector<f16> pw(2 * total);
+      for (int l = 0; l < BLAYERS; ++l)
+        for (int m = 0; m < 4; ++m) {
+          const size_t off = WT_LAYER * l + WT_OFF[m];
+          const int K = m == 3 ? BI : BH;
+          const size_t N = WT_SIZE[m] / K;
+          for (size_t r = 0; r < N; ++r)
+            for (int k = 0; k < K; ++k) {
+              pw[2 * off + x3_pair_index(r, k, K, 0)] = hl[off + r * K + k];
+              pw[2 * off + x3_pair_index(r, k, K, 1)] = hl[total + off + r * K + k];
+            }
+        }
+      hl.swap(pw);
+    }
     MEC_TRY(upload(wts, hl.data(), hl.size() * sizeof(f16)));
   } else if (f32) {
     MEC_TRY(upload(wts32, w32.data(), w32.size() * sizeof(float)));

@@ -304,14 +304,29 @@ int TextModel::forward_x3(const int32_t* ids, const int32_t* mask, int B, int L,
     st1c = c.take<float2>(NS * 2);
   }));
   const int M = tb.M, NS = tb.NS;
-  const long long MH = (long long)M * BH, NSH = (long long)NS * BH;  // lo-plane offsets of [M,768] / [NS,768] planes
+  // x3_layout 1: every split tensor below (weights, LN outputs, context, FFN intermediate, the last layer's
+  // K | V and [CLS]-row buffers) is paired ([rows][2K], mec_common.h x3_pair_index) in the same buffers; a
+  // lo-plane offset is then kX3Paired and the weight matrices sit at twice their planar offsets
+  const bool pr = x3_paired;
+  auto plo = [&](long long planar) { return pr ? kX3Paired : planar; };
+  const long long MH = plo((long long)M * BH), NSH = plo((long long)NS * BH);  // lo planes of [M,768] / [NS,768]
   float2* st2 = st1 + M;
   float2* st2c = st1c + NS;
   const bool cls_last = opt().bert_cls_last != 0;
   const int gelu_act = opt().gelu_x3 ? ACT_GELU_F32 : ACT_GELU_EXACT;  // FFN1's erf GELU
   const f16* W = wts.as<f16>();
   const float* P = prm.as<float>();
-  const long long wlo = (long long)x3_lo;
+  const long long wlo = plo((long long)x3_lo);
+  auto wmat = [&](const f16* w) { return pr ? W + 2 * (w - W) : w; };  // a weight matrix of layer_weights(W, l)
+  // split operands A (lo plane a_lo on) and weight matrix w of g, planar or paired
+  auto operands = [&](GemmParams& g, const f16* A, long long a_lo, const f16* w) {
+    g.split = 1; g.A = A; g.B = wmat(w);
+    if (pr) { g.a_pair = g.b_pair = 1; } else { g.a_lo = a_lo; g.b_lo = wlo; }
+  };
+  auto planes_out = [&](GemmParams& g, f16* C, long long c_lo) {
+    g.C16 = C;
+    if (pr) g.c_pair = 1; else g.c_lo = c_lo;
+  };
 
   // Deferred LayerNorm (as on the f16 path): the LN kernels write the GEMM operand planes and the row
   // (mean, rstd) only; the f32 LN output is needed only as the next residual, which the O-proj / FFN2
@@ -326,25 +341,25 @@ int TextModel::forward_x3(const int32_t* ids, const int32_t* mask, int B, int L,
     const long long nh = (long long)r.n * BH, nf = (long long)r.n * BI;
     auto tag = [&](int t) { return r.tagged ? t : (int)TAG_NONE; };
     GemmParams g;
-    g.split = 1; g.A = r.ctx; g.a_lo = nh; g.B = w.wo; g.b_lo = wlo; g.oscale = x.scale[1];
+    operands(g, r.ctx, nh, w.wo); g.oscale = x.scale[1];
     g.bias = p.bo; g.R = r.h32; g.r_f32 = 1; g.C32 = r.t32; g.M = r.n; g.N = BH; g.K = BH;
     if (r.deferred_in) { g.r_stats = r.st2; g.r_g = layer_params(P, l - 1).g2; g.r_b = layer_params(P, l - 1).b2; }
     MEC_TRY(launch_gemm(g, s, &prof, tag(TAG_BERT_OPROJ)));
     MEC_TRY(prof.begin(tag(TAG_BERT_LN), s));
-    MEC_TRY(launch_bert_layernorm(r.t32, r.n, p.g1, p.b1, nullptr, r.op, r.st1, s, nh, std::ldexp(1.0f, x.s_ln1)));
+    MEC_TRY(launch_bert_layernorm(r.t32, r.n, p.g1, p.b1, nullptr, r.op, r.st1, s, plo(nh), std::ldexp(1.0f, x.s_ln1)));
     MEC_TRY(prof.end(tag(TAG_BERT_LN), s));
     g = GemmParams();
-    g.split = 1; g.A = r.op; g.a_lo = nh; g.B = w.wi; g.b_lo = wlo; g.oscale = x.scale[2];
-    g.bias = p.bi; g.act = gelu_act; g.C16 = r.ffn; g.c_lo = nf; g.cscale = std::ldexp(1.0f, x.s_ffn);
+    operands(g, r.op, nh, w.wi); g.oscale = x.scale[2];
+    g.bias = p.bi; g.act = gelu_act; planes_out(g, r.ffn, nf); g.cscale = std::ldexp(1.0f, x.s_ffn);
     g.M = r.n; g.N = BI; g.K = BH;
     MEC_TRY(launch_gemm(g, s, &prof, tag(TAG_BERT_FFN1)));
     g = GemmParams();
-    g.split = 1; g.A = r.ffn; g.a_lo = nf; g.B = w.wo2; g.b_lo = wlo; g.oscale = x.scale[3];
+    operands(g, r.ffn, nf, w.wo2); g.oscale = x.scale[3];
     g.bias = p.bo2; g.R = r.t32; g.r_f32 = 1; g.r_stats = r.st1; g.r_g = p.g1; g.r_b = p.b1; g.C32 = r.h32;
     g.M = r.n; g.N = BH; g.K = BI;
     MEC_TRY(launch_gemm(g, s, &prof, tag(TAG_BERT_FFN2)));
     MEC_TRY(prof.begin(tag(TAG_BERT_LN), s));
-    MEC_TRY(launch_bert_layernorm(r.h32, r.n, p.g2, p.b2, r.full_out ? r.h32 : nullptr, r.op, r.st2, s, nh,
+    MEC_TRY(launch_bert_layernorm(r.h32, r.n, p.g2, p.b2, r.full_out ? r.h32 : nullptr, r.op, r.st2, s, plo(nh),
                                   std::ldexp(1.0f, x.s_ln2)));
     MEC_TRY(prof.end(tag(TAG_BERT_LN), s));
     return 0;
@@ -362,15 +377,18 @@ int TextModel::forward_x3(const int32_t* ids, const int32_t* mask, int B, int L,
     GemmParams g;
     if (cls_last && last) {
       // [CLS]-only last layer (TextModel::forward): K / V for every token, the rest on the [CLS] rows
-      MEC_TRY(gather_cls_rows(
-          tb, {{h32, h32c, BH * 4}, {hs, hsc, BH * 2}, {hs + MH, hsc + NSH, BH * 2}, {st2, st2c, 8}}, s));
-      const long long kvlo = (long long)M * 2 * BH;
-      g.split = 1; g.A = hs; g.a_lo = MH; g.B = w.wqkv + (size_t)BH * BH; g.b_lo = wlo; g.oscale = x.scale[0];
-      g.bias = bqkv + BH; g.C16 = bigs; g.c_lo = kvlo; g.M = M; g.N = 2 * BH; g.K = BH;
+      if (pr)  // a paired row holds both planes
+        MEC_TRY(gather_cls_rows(tb, {{h32, h32c, BH * 4}, {hs, hsc, BH * 4}, {st2, st2c, 8}}, s));
+      else
+        MEC_TRY(gather_cls_rows(
+            tb, {{h32, h32c, BH * 4}, {hs, hsc, BH * 2}, {hs + MH, hsc + NSH, BH * 2}, {st2, st2c, 8}}, s));
+      const long long kvlo = plo((long long)M * 2 * BH);
+      operands(g, hs, MH, w.wqkv + (size_t)BH * BH); g.oscale = x.scale[0];
+      g.bias = bqkv + BH; planes_out(g, bigs, kvlo); g.M = M; g.N = 2 * BH; g.K = BH;
       MEC_TRY(launch_gemm(g, s, &prof, TAG_NONE));  // K | V planes [M, 1536]
       g = GemmParams();
-      g.split = 1; g.A = hsc; g.a_lo = NSH; g.B = w.wqkv; g.b_lo = wlo; g.oscale = x.scale[0];
-      g.bias = bqkv; g.C16 = qsc; g.c_lo = NSH; g.M = NS; g.N = BH; g.K = BH;
+      operands(g, hsc, NSH, w.wqkv); g.oscale = x.scale[0];
+      g.bias = bqkv; planes_out(g, qsc, NSH); g.M = NS; g.N = BH; g.K = BH;
       MEC_TRY(launch_gemm(g, s, &prof, TAG_NONE));  // Q planes of the [CLS] rows
       MEC_TRY(launch_bert_attention_x3_cls(bigs, kvlo, tb.mask, qsc, NSH, csc, NSH, NS, qks, s, tb.cidx));
       MEC_TRY(tail(l, {NS, h32c, t32c, csc, hsc, fsc, st1c, st2c, /*deferred_in=*/true, /*full_out=*/true, /*tagged=*/false}));
@@ -381,12 +399,12 @@ int TextModel::forward_x3(const int32_t* ids, const int32_t* mask, int B, int L,
     // and every split product of the forward keeps one term order
     if (opt().bert_qkv_attn == 1 && L == ATT_L && opt().gemm_x3_order == 1) {
       MEC_TRY(prof.begin(TAG_BERT_QKV, s));
-      MEC_TRY(launch_bert_qkv_attn_x3(hs, MH, w.wqkv, wlo, x.scale[0], bqkv, tb.mask, cs, MH, B, qks, s, pk != nullptr));
+      MEC_TRY(launch_bert_qkv_attn_x3(hs, MH, wmat(w.wqkv), wlo, x.scale[0], bqkv, tb.mask, cs, MH, B, qks, s, pk != nullptr));
       MEC_TRY(prof.end(TAG_BERT_QKV, s));
     } else {
-      const long long qlo = (long long)M * BQKV;
-      g.split = 1; g.A = hs; g.a_lo = MH; g.B = w.wqkv; g.b_lo = wlo; g.oscale = x.scale[0];
-      g.bias = bqkv; g.C16 = bigs; g.c_lo = qlo; g.M = M; g.N = BQKV; g.K = BH;
+      const long long qlo = plo((long long)M * BQKV);
+      operands(g, hs, MH, w.wqkv); g.oscale = x.scale[0];
+      g.bias = bqkv; planes_out(g, bigs, qlo); g.M = M; g.N = BQKV; g.K = BH;
       MEC_TRY(launch_gemm(g, s, &prof, TAG_BERT_QKV));
       MEC_TRY(prof.begin(TAG_BERT_ATTN, s));
       MEC_TRY(launch_bert_attention_x3(bigs, qlo, tb.mask, cs, MH, B, qks, s, pk != nullptr));

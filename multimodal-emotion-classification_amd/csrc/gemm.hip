@@ -48,10 +48,18 @@ int set_conv_geometry(GemmParams& g, int n) {
 
 int launch_gemm(const GemmParams& p0, hipStream_t s, Prof* prof, int tag) {
   GemmParams p = p0;
-  if (p.c_lo && !p.ovf) p.ovf = range_flag();  // split output: the calling handle's range flag
+  if ((p.c_lo || p.c_pair) && !p.ovf) p.ovf = range_flag();  // split output: the calling handle's range flag
+  if (p.a_pair || p.b_pair || p.c_pair) {  // paired planes: the K-interleaved engine's plain-A tiles only
+    MEC_REQUIRE(p.split && opt().gemm_x3_order == 1, "gemm: paired planes need split operands in the K-interleaved order");
+    MEC_REQUIRE(p.a_pair && p.b_pair, "gemm: A and B are paired together (one stage layout)");
+    MEC_REQUIRE(p.amode == A_PLAIN && !p.r_lo, "gemm: paired planes take a plain A and no split residual");
+    MEC_REQUIRE(!p.c_pair || p.C16, "gemm: c_pair lays out the f16 hi / lo output");
+  }
   MEC_REQUIRE(p.M > 0 && p.N > 0 && p.K > 0, "gemm: empty shape");
   MEC_REQUIRE(p.N % 64 == 0, "gemm: N % 64 != 0");
-  MEC_REQUIRE(p.K % GBK == 0, "gemm: K % 64 != 0");
+  // (the K-interleaved split tiles step K by 32; every other tile by 64)
+  MEC_REQUIRE(p.K % ((p.split && opt().gemm_x3_order == 1 && p.amode == A_PLAIN) ? 32 : GBK) == 0,
+              "gemm: K % 64 != 0 (K-interleaved split operands, plain A: K % 32 != 0)");
   MEC_REQUIRE(p.A && p.B, "gemm: null operand");
   MEC_REQUIRE(p.C16 || p.C32, "gemm: no output");
   MEC_REQUIRE(!p.r_stats || (p.R && p.r_f32 && p.r_g && p.r_b), "gemm: deferred-LN residual needs f32 R, gamma, beta");
@@ -73,6 +81,9 @@ int launch_gemm(const GemmParams& p0, hipStream_t s, Prof* prof, int tag) {
     // pinned tile's grid fills half the chip; the pass-major order pins FFN1 to 10256 (it and the ping-pong
     // tile time within 3-7 %, tools/bench_split.py)
     int pin = (tag > 0 && tag < TAG_COUNT) ? opt().gemm_x3_tag[tag] : 0;
+    // paired planes: the one-stage tile's loader holds twice the source pointers and spills (FFN2 at B = 256:
+    // 537 us against 456 planar), while the 256 x 256 ring gains (442 against 465): profiles/r07_x3_paired_gemm.txt
+    if (pin == 72128 && p.a_pair) pin = 70256;
     if (pin) {
       const int bm = (pin / 1000) % 10 == 1 ? 128 : 256, bn = pin % 1000;
       // the one-stage 72128 tile pays off only with two workgroups on every CU (BERT B = 256: 768 tiles); at

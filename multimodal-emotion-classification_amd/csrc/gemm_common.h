@@ -305,7 +305,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, accv (&acc)[T
       }
       if (row < M && (!NOSTORE || v[0] == 1234.5f)) {
         const size_t base = (size_t)row * N + col0;
-        if (p.C16 && p.c_lo) {  // split output: planes of v * cscale, the lo plane carries the rest
+        if (p.C16 && (p.c_lo || p.c_pair)) {  // split output: planes of v * cscale, the lo plane carries the rest
           float u[8];
 #pragma unroll
           for (int q = 0; q < 8; ++q) u[q] = v[q];
@@ -320,8 +320,15 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, accv (&acc)[T
             l[q] = (f16)(u[q] - (float)h[q]);
             x3bad |= x3_out_of_range(u[q]);
           }
-          *reinterpret_cast<half8*>(p.C16 + base) = h;
-          *reinterpret_cast<half8*>(p.C16 + p.c_lo + base) = l;
+          if (p.c_pair) {  // paired planes: the lane's 8 columns sit in one 32-column chunk (col0 % 8 == 0), so
+            // four adjacent lanes write one whole 128-B line
+            f16* o = p.C16 + x3_pair_index(row, col0, N, 0);
+            *reinterpret_cast<half8*>(o) = h;
+            *reinterpret_cast<half8*>(o + 32) = l;
+          } else {
+            *reinterpret_cast<half8*>(p.C16 + base) = h;
+            *reinterpret_cast<half8*>(p.C16 + p.c_lo + base) = l;
+          }
         } else if (p.C16) {
           half8 h;
 #pragma unroll
@@ -336,7 +343,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, accv (&acc)[T
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   }
-  if (p.c_lo) x3_raise(p.ovf, x3bad);
+  if (p.c_lo || p.c_pair) x3_raise(p.ovf, x3bad);
 }
 
 }  // namespace mec

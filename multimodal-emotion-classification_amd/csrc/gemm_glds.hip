@@ -44,15 +44,23 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4) ? 2 : 1) void gemm_gld
   // (two halves), and each 32-deep k chunk runs its three MFMA terms (lo.hi, hi.lo, hi.hi) back to
   // back: every operand byte is fetched and staged once instead of 1.5 times on average, and four
   // fragment reads feed three MFMAs instead of six. 16x16x32 tiles only (one k-chunk order).
+  // SP = 3 (paired, GemmParams::a_pair / b_pair): SP = 2's loop on operands stored [rows][2K], each
+  // 32-deep K chunk's hi halfs followed by its lo halfs. A stage is [BM + BN] rows of 64 halfs (hi in
+  // chunks 0-3, lo in 4-7), filled by 8-row x 128-B pieces (whole cache lines; SP = 2's 16-row x 64-B
+  // pieces take half lines of one plane) and swizzled with sw<64>; the fragment of plane h is chunk
+  // 4 h + lq, the f16 BK = 64 path's address pattern. Same piece count, fragments and MFMA order as
+  // SP = 2: same bits. Plain A only.
   static_assert(BK == 64 || BK == 32, "BK");
   static_assert(SP == 0 || PRE == 0 || PRE == 3, "split operands: split residual prefetch only");
-  static_assert(SP != 2 || MF == 16, "interleaved split: 16x16x32 tiles only");
+  static_assert(SP < 2 || MF == 16, "interleaved split: 16x16x32 tiles only");
+  static_assert(SP != 3 || (BK == 32 && AM == A_PLAIN && PRE == 0), "paired split: 32-deep stages, plain A");
   // NS = 1 (tile 72128, interleaved split operands): one stage, read whole into fragment registers; once every
   // wave holds them the stage is refilled for step t + 1 under step t's MFMAs (bert_qkv_attn_x3_kernel's
   // schedule). 48 KB of LDS lets two workgroups share a CU, so one's barriers, loads and epilogue run under
   // the other's MFMAs. Same fragments, same MFMA order as the ring tiles: same bits.
-  static_assert(NS != 1 || (SP == 2 && BK == 32 && DBG == 0), "one-stage tile: interleaved split operands only");
-  constexpr int CH = BK / 8;                   // 16-B chunks per LDS row
+  static_assert(NS != 1 || (SP >= 2 && BK == 32 && DBG == 0), "one-stage tile: interleaved split operands only");
+  constexpr int LBK = SP == 3 ? 64 : BK;       // halfs per LDS row (paired: a K chunk's hi and lo halfs)
+  constexpr int CH = LBK / 8;                  // 16-B chunks per LDS row
   constexpr int RPI = 64 / CH;                 // rows per glds wave-instruction (1 KB)
   constexpr int NW = WM * WN;
   static_assert(NW == 8 || NW == 4, "4 or 8 waves");
@@ -65,7 +73,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4) ? 2 : 1) void gemm_gld
   static_assert(BI >= 1 && AI >= 1, "tile too small for 8 waves");
   constexpr int NPL = SP == 2 ? 2 : 1;         // operand planes per stage
   constexpr int LPT = (AI + BI) * NPL;
-  constexpr int HALF = (BM + BN) * BK;         // halfs per plane of a stage
+  constexpr int HALF = (BM + BN) * LBK;        // halfs per plane of a stage (paired: the whole stage)
   constexpr int STAGE = HALF * NPL;            // halfs per stage
   constexpr int EPI_LD = TN + 4;               // f32 staging row (padded)
   constexpr int EPI = NW * 32 * EPI_LD;        // floats for the epilogue staging
@@ -76,6 +84,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4) ? 2 : 1) void gemm_gld
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN, wn = wave - (wave / WN) * WN;
   const int M = p.M, N = p.N, K = p.K;
+  const int LDK = SP == 3 ? 2 * K : K;  // halfs per operand row in memory
   const int nbn = N / BN;
   const int nbm = (M + BM - 1) / BM;
   const int nwg = nbm * nbn;
@@ -100,9 +109,9 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4) ? 2 : 1) void gemm_gld
     const int m = m0 + r;
     a_ok[i] = m < M;
     const int mc = a_ok[i] ? m : 0;
-    const int kc = sw<BK>(r, pchunk);
+    const int kc = sw<LBK>(r, pchunk);
     if constexpr (AM == A_PLAIN) {
-      a_src[i] = reinterpret_cast<const f16*>(p.A) + (size_t)mc * K + kc * 8;
+      a_src[i] = reinterpret_cast<const f16*>(p.A) + (size_t)mc * LDK + kc * 8;
     } else if constexpr (AM == A_DUAL) {
       a_src[i] = reinterpret_cast<const f16*>(p.A) + (size_t)mc * p.K1 + kc * 8;
       const int ohw = p.OH * p.OW;
@@ -127,8 +136,8 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4) ? 2 : 1) void gemm_gld
 #pragma unroll
   for (int j = 0; j < BI; ++j) {
     const int r = (wave * BI + j) * RPI + lrow;
-    const int kc = sw<BK>(r, pchunk);
-    b_src[j] = p.B + (size_t)(n0 + r) * K + kc * 8;
+    const int kc = sw<LBK>(r, pchunk);
+    b_src[j] = p.B + (size_t)(n0 + r) * LDK + kc * 8;
   }
   const f16* zero = reinterpret_cast<const f16*>(g_zero_page);
 
@@ -136,21 +145,21 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4) ? 2 : 1) void gemm_gld
   // one plane of K tile kt into stage `stage` (its half h): A at aoff, B at boff from the hi planes (glds16:
   // the fragment reads below keep counted lgkmcnt waits)
   auto issue_plane = [&](int stage, int kt, int h, long long aoff, long long boff) {
-    const int k0 = kt * BK;
+    const int k0 = kt * LBK;
     f16* sA = smem + stage * STAGE + h * HALF;
-    f16* sB = sA + BM * BK;
+    f16* sB = sA + BM * LBK;
     if constexpr (AM == A_PLAIN) {
 #pragma unroll
       for (int i = 0; i < AI; ++i) {
         const f16* src = a_ok[i] ? a_src[i] + aoff + k0 : zero;
-        glds16(src, (lds_vptr)(sA + (wave * AI + i) * RPI * BK));
+        glds16(src, (lds_vptr)(sA + (wave * AI + i) * RPI * LBK));
       }
     } else if constexpr (AM == A_DUAL) {
       const bool first = k0 < p.K1;
 #pragma unroll
       for (int i = 0; i < AI; ++i) {  // split: both sources' lo planes at the same offset a_lo
         const f16* src = !a_ok[i] ? zero : (first ? a_src[i] + aoff + k0 : a2_src[i] + aoff + (k0 - p.K1));
-        glds16(src, (lds_vptr)(sA + (wave * AI + i) * RPI * BK));
+        glds16(src, (lds_vptr)(sA + (wave * AI + i) * RPI * LBK));
       }
     } else {
       const int tap = k0 / p.C;
@@ -162,12 +171,12 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4) ? 2 : 1) void gemm_gld
         const int ih = a_ih0[i] + kh, iw = a_iw0[i] + kw;
         const bool ok = a_ok[i] && ih >= 0 && ih < p.H && iw >= 0 && iw < p.W;
         const f16* src = ok ? a_src[i] + aoff + ((size_t)ih * p.W + iw) * p.C + c0 : zero;
-        glds16(src, (lds_vptr)(sA + (wave * AI + i) * RPI * BK));
+        glds16(src, (lds_vptr)(sA + (wave * AI + i) * RPI * LBK));
       }
     }
 #pragma unroll
     for (int j = 0; j < BI; ++j)
-      glds16(b_src[j] + boff + k0, (lds_vptr)(sB + (wave * BI + j) * RPI * BK));
+      glds16(b_src[j] + boff + k0, (lds_vptr)(sB + (wave * BI + j) * RPI * LBK));
   };
   auto issue = [&](int stage, int kt) {
     if constexpr (SP == 1) {  // pass 0: A_lo . B_hi, pass 1: A_hi . B_lo, pass 2: A_hi . B_hi
@@ -176,9 +185,14 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4) ? 2 : 1) void gemm_gld
     } else if constexpr (SP == 2) {  // hi planes into half 0, lo planes into half 1
       issue_plane(stage, kt, 0, 0, 0);
       issue_plane(stage, kt, 1, p.a_lo, p.b_lo);
-    } else {
+    } else {  // (paired: one 128-B row piece carries both planes)
       issue_plane(stage, kt, 0, 0, 0);
     }
+  };
+  // fragment of plane h (0 hi, 1 lo) of stage row r, 16-B k chunk kcs, in the A or B tile at s
+  auto frag = [&](const f16* s, int h, int r, int kcs) {
+    if constexpr (SP == 3) return *reinterpret_cast<const half8*>(s + r * 64 + sw<64>(r, 4 * h + kcs) * 8);
+    else return *reinterpret_cast<const half8*>(s + h * HALF + r * BK + sw<BK>(r, kcs) * 8);
   };
 
   using EG = EpiGeom<BM, BN, WM, WN>;
@@ -225,19 +239,19 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4) ? 2 : 1) void gemm_gld
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
       const f16* sA = smem;
-      const f16* sB = sA + BM * BK;
+      const f16* sB = sA + BM * LBK;
       half8 af[2][TI], bf[2][TJ];  // [plane: 0 hi, 1 lo]
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
 #pragma unroll
         for (int i = 0; i < TI; ++i) {
           const int r = wm * TM + i * 16 + l16;
-          af[h][i] = *reinterpret_cast<const half8*>(sA + h * HALF + r * BK + sw<BK>(r, lq) * 8);
+          af[h][i] = frag(sA, h, r, lq);
         }
 #pragma unroll
         for (int j = 0; j < TJ; ++j) {
           const int r = wn * TN + j * 16 + l16;
-          bf[h][j] = *reinterpret_cast<const half8*>(sB + h * HALF + r * BK + sw<BK>(r, lq) * 8);
+          bf[h][j] = frag(sB, h, r, lq);
         }
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -294,7 +308,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4) ? 2 : 1) void gemm_gld
     // its hi planes after lo.hi and lo planes after hi.lo; every wave issuing right after the barrier; MFMA
     // sections at wave priority 1; an early restage of the 2-stage rings; a start stagger between the
     // workgroups sharing a CU)
-    const bool late = SP == 2 && wave >= NW / 2;
+    const bool late = SP >= 2 && wave >= NW / 2;
     const bool nxt = DBG != 1 && t + NS - 1 < nk;
     if (nxt && !late) issue((t + NS - 1) % NS, t + NS - 1);
     auto issue_late = [&]() {
@@ -303,7 +317,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4) ? 2 : 1) void gemm_gld
       __builtin_amdgcn_sched_barrier(0);
     };
     const f16* sA = smem + ((DBG == 1 ? 0 : t) % NS) * STAGE;
-    const f16* sB = sA + BM * BK;
+    const f16* sB = sA + BM * LBK;
     if constexpr (MF == 32) {
 #pragma unroll
       for (int s = 0; s < BK / 16; ++s) {
@@ -325,7 +339,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4) ? 2 : 1) void gemm_gld
           for (int j = 0; j < TJ; ++j)
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[i], bf[j], acc[i][j], 0, 0, 0);
       }
-    } else if constexpr (SP == 2) {
+    } else if constexpr (SP >= 2) {
       // interleaved split: per 32-deep k chunk the hi and lo fragments of A and B, then the three
       // terms term-major (each accumulator: lo.hi, hi.lo, hi.hi of the chunk, in that order).
       // The fragment reads go in two groups, each ahead of the terms that consume it: (B hi, A lo) for
@@ -347,14 +361,14 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4) ? 2 : 1) void gemm_gld
 #pragma unroll
           for (int i = 0; i < TI; ++i) {
             const int r = wm * TM + i * 16 + l16;
-            af[h][i] = *reinterpret_cast<const half8*>(sA + h * HALF + r * BK + sw<BK>(r, kcs) * 8);
+            af[h][i] = frag(sA, h, r, kcs);
           }
         };
         auto read_b = [&](int h) {
 #pragma unroll
           for (int j = 0; j < TJ; ++j) {
             const int r = wn * TN + j * 16 + l16;
-            bf[h][j] = *reinterpret_cast<const half8*>(sB + h * HALF + r * BK + sw<BK>(r, kcs) * 8);
+            bf[h][j] = frag(sB, h, r, kcs);
           }
         };
         read_b(0);
@@ -849,7 +863,9 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmParams p) {
 // K-interleaved split operands (16x16x32, 32-deep stages) in each A mode
 template <int BM, int BN, int WM, int WN, int NS, int BK>
 static int launch_x3i(const GemmParams& p, hipStream_t s, int nwg, dim3 blk) {
-  if (BM * BN <= 128 * 128 && opt().gemm_prefetch_r && p.amode == A_PLAIN && p.R && p.r_lo && p.K <= 512) {
+  if (p.a_pair) {  // paired planes (launch_gemm: plain A, both operands paired, no split residual)
+    hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, WM, WN, NS, A_PLAIN, 0, 16, BK, 0, -1, 3>), dim3(nwg), blk, 0, s, p);
+  } else if (BM * BN <= 128 * 128 && opt().gemm_prefetch_r && p.amode == A_PLAIN && p.R && p.r_lo && p.K <= 512) {
     if constexpr (BM * BN <= 128 * 128)
       hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, WM, WN, NS, A_PLAIN, 0, 16, BK, 3, -1, 2>), dim3(nwg), blk, 0, s, p);
   } else if (p.amode == A_PLAIN)
@@ -914,7 +930,7 @@ static int launch_cfg(const GemmParams& p0, hipStream_t s) {
   // (gemm_debug 3: the epilogue without its stores; 6: with a plain (no GELU) epilogue -- prices the GELU)
   if constexpr (BM == 256 && BN == 256) {  // the 256 x 256 tiles only
     if ((opt().gemm_debug == 1 || opt().gemm_debug == 2 || opt().gemm_debug == 3 || opt().gemm_debug == 6) &&
-        p.split == 2 && p.amode == A_PLAIN) {
+        p.split == 2 && p.amode == A_PLAIN && !p.a_pair) {
       if constexpr (MF == 16 && BK == 32 && 4 * (BM + BN) * BK * NS <= 160 * 1024) {
         if (opt().gemm_debug == 1)
           hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, WM, WN, NS, A_PLAIN, 1, MF, BK, 0, -1, 2>), dim3(nwg), blk, 0, s, p);
@@ -954,8 +970,8 @@ static int launch_cfg(const GemmParams& p0, hipStream_t s) {
 // being captured into a graph) and caches the fastest; `gemm_bn` forces a width.
 // Cache key: engine 0 (this engine) + the shape; the cache is the calling handle's
 // (tune_cache(), mec_common.h).
-static std::array<int, 11> gemm_key(const GemmParams& p) {  // engine slot: 0, 2 split pass-major, 3 interleaved
-  return {p.split == 2 ? 3 : p.split ? 2 : 0, p.amode, p.M, p.N, p.K, p.H, p.W, p.C, p.ks, p.stride, p.pad};
+static std::array<int, 11> gemm_key(const GemmParams& p) {  // engine slot: 0, 2 split pass-major, 3 interleaved, 4 paired
+  return {p.split == 2 ? (p.a_pair ? 4 : 3) : p.split ? 2 : 0, p.amode, p.M, p.N, p.K, p.H, p.W, p.C, p.ks, p.stride, p.pad};
 }
 
 // Tile configs (id): 256 / 128 / 64 = 256 x BN with 8 waves; 1128 / 1064 = 128 x BN with
@@ -1113,7 +1129,8 @@ static int tune_bn(const GemmParams& p, hipStream_t s, int* out_bn) {
 int gemm_tuned_bn(int amode, int M, int N, int K) {
   int t = tune_cache().find_shape(0, amode, M, N, K);
   if (!t) t = tune_cache().find_shape(2, amode, M, N, K);  // else the split-operand engines'
-  return t ? t : tune_cache().find_shape(3, amode, M, N, K);
+  if (!t) t = tune_cache().find_shape(3, amode, M, N, K);
+  return t ? t : tune_cache().find_shape(4, amode, M, N, K);
 }
 
 int launch_gemm_glds(const GemmParams& p0, hipStream_t s, int force_bn) {

@@ -141,6 +141,11 @@ struct Options {
   // binades above the bound / BN estimate before the range flag trips. engine.HipModel re-creates a handle
   // with more headroom after a trip (the batch itself is re-run on the fp32 engine)
   int x3_headroom = 0;
+  // fp32x3 text model, read when a handle is created: 1 = weight and activation planes paired (GemmParams::a_pair:
+  // [rows][2K], each 32-element K chunk's hi halfs then its lo halfs, so every operand DMA takes whole 128-B
+  // lines), 0 = planar (hi plane, then lo plane). Same bits. Paired needs the K-interleaved term order: a handle
+  // created with gemm_x3_order 0 is planar
+  int x3_layout = 1;
   // fp32x3 MobileNetV2 fused blocks: the expanded chunk's f32 rows with a per-tile-shape 16-B chunk swizzle
   // (1; fewer LDS bank conflicts on the depthwise reads) or unswizzled 36-float rows (0); same bits
   int mbv2_x3_sesw = 1;
@@ -361,7 +366,24 @@ struct GemmParams {
   float cscale = 1.f;
   unsigned* ovf = nullptr;  // split output's range flag (x3_raise); launch_gemm fills in range_flag()
   long long r_lo = 0;  // != 0: the f16 residual R is a hi plane + a lo plane at R + r_lo (R = hi + lo)
+  // Paired split planes (K-interleaved engine, plain A): a split tensor X[rows][K], K % 32 == 0, stored as
+  // one f16 array [rows][2K] holding, per 32-element K chunk, the chunk's hi halfs then its lo halfs
+  // (x3_pair_index below), so one row's operands of one 32-deep K step are one aligned 128-B line. Same
+  // values and scales as the planar form, only the addresses move; a_lo / b_lo / c_lo are then unused.
+  // a_pair and b_pair go together (one stage layout); c_pair lays the c_lo-style output out the same way.
+  int a_pair = 0, b_pair = 0, c_pair = 0;
 };
+
+// Paired split planes: index of element (r, k) of plane p (0 hi, 1 lo) of a [rows][K] tensor.
+__host__ __device__ inline size_t x3_pair_index(size_t r, int k, int K, int p) {
+  return r * 2 * (size_t)K + (size_t)(k >> 5) * 64 + p * 32 + (k & 31);
+}
+// The text kernels locate a split tensor's lo plane by an element offset `lo` > 0 from its hi plane; kX3Paired
+// in that place says the tensor is paired. x3_at: index of element (r, k) of plane p either way.
+constexpr long long kX3Paired = -1;
+__host__ __device__ inline size_t x3_at(long long lo, size_t r, int k, int K, int p) {
+  return lo < 0 ? x3_pair_index(r, k, K, p) : (size_t)(p ? lo : 0) + r * (size_t)K + k;
+}
 
 // conv / dual geometry (gemm.hip): what both engines require of ks, stride, pad and the extents before a
 // launch; and the C-ABI entries' form, which validates n and the rest before dividing by stride and sets

@@ -126,6 +126,9 @@ struct TextModel : Model {
     float scale[4] = {1.f, 1.f, 1.f, 1.f};
   };
   size_t x3_lo = 0;
+  // x3_layout 1 (with the K-interleaved term order): wts holds every matrix [N][K] paired, [N][2K] at twice its
+  // planar offset (mec_common.h x3_pair_index), and every activation tensor of the forward is paired too
+  bool x3_paired = false;
   int x3_s_emb = 0;
   std::vector<X3Layer> x3_layers;
   DevBuf x3b;
