@@ -142,6 +142,58 @@ int mec_text_fwd_packed(mec_model* m, const int32_t* ids, const int32_t* row, co
 int mec_text_lstm_fwd(mec_model* m, const int32_t* ids, int B, int L, float* feat, float* logits, float* probs,
                       void* stream);
 
+/* Tokenization on the GPU for both text paths: UTF-8 bytes in, ids / mask / len on the device. A
+ * tokenizer is an object of its own (not a mec_model): its creation data is a vocabulary, not an fp32 blob.
+ * The vocabulary is given on the HOST as n entries, entry e = the bytes pool[off[e] .. off[e+1]) -> id[e];
+ * creation builds an open-addressing hash table over them (load factor <= 1/2) and uploads it with the
+ * byte pool. A hash hit is always confirmed by comparing the bytes, so a collision never yields a wrong id.
+ *
+ * MEC_TOK_KERAS restates keras Tokenizer.texts_to_sequences + pad_sequences(padding='post',
+ * truncating='post') as the BiLSTM path calls them (inference/text_lstm_inference.py:61-62), on the bytes
+ * of the already lower-cased text: words are the maximal runs of bytes b with delim[b] == 0; each word in
+ * order writes its id when it is in the table, else oov_id when oov_id >= 0, else nothing; stop after L
+ * ids, fill the row with 0; len = ids written, mask[j] = j < len.
+ *
+ * MEC_TOK_WORDPIECE restates transformers 4.30's BertTokenizer (BasicTokenizer + WordpieceTokenizer,
+ * text_inference.py:78-85) for 7-BIT input (the caller keeps other texts on the host): bytes 0x00,
+ * 0x01-0x1F other than \t \n \r, and 0x7F are dropped; \t \n \r and space separate words; A-Z folds to a-z
+ * when `lower`; every punctuation byte (33-47, 58-64, 91-96, 123-126) is a word of its own; a word longer
+ * than max_word is unk_id, else greedy longest-match-first, plain entries at word position 0 and, later in
+ * the word, entries whose pool form starts with "##" (the prefix is stripped into a flag at creation); a
+ * word with an unmatched position is one unk_id. The row is cls_id, the first L-2 pieces, sep_id, then
+ * pad_id; len counts cls_id and sep_id, mask[j] = j < len. */
+typedef struct mec_tokenizer mec_tokenizer;
+enum { MEC_TOK_KERAS = 0, MEC_TOK_WORDPIECE = 1 };
+typedef struct mec_tok_desc {
+  int kind;             /* MEC_TOK_KERAS or MEC_TOK_WORDPIECE */
+  const uint8_t* pool;  /* HOST: the entries' bytes, back to back */
+  const int64_t* off;   /* HOST: n + 1 monotone offsets into pool, off[0] >= 0 */
+  const int32_t* id;    /* HOST: n ids, each >= 0 */
+  int n;
+  uint8_t delim[256];   /* KERAS: 1 = this byte separates words */
+  int oov_id;           /* KERAS: id written for a word not in the table; -1 = such words are dropped */
+  int lower;            /* WORDPIECE: fold A-Z to a-z */
+  int unk_id, cls_id, sep_id, pad_id; /* WORDPIECE */
+  int max_word;         /* WORDPIECE: 1..128 (transformers: 100) */
+} mec_tok_desc;
+/* Returns -1 (mec_last_error says why) for a null pointer, an unknown kind, n < 0, non-monotone off, an
+ * entry longer than 65535 bytes, a duplicate entry, an id < 0, oov_id < -1 and, WORDPIECE only, an entry
+ * holding a byte >= 0x80, a special id < 0 or max_word outside 1..128. Nothing of the descriptor is
+ * referenced after the call returns. */
+int mec_tok_create(const mec_tok_desc* d, int device, mec_tokenizer** out);
+/* text u8 and text_off int64[B+1] are DEVICE pointers: text i is the bytes text[text_off[i] ..
+ * text_off[i+1]), and text_off[B] is the blob's size. Outputs (device) ids int32[B,L], mask int32[B,L] or
+ * NULL, len int32[B] or NULL; 1 <= L <= 512 (WORDPIECE: 2 <= L). B == 0 returns 0 without a launch; a null
+ * tokenizer, text, text_off or ids, B < 0 or L out of range return -1 before any launch. Asynchronous on
+ * `stream`; allocates nothing, never synchronizes, can be captured into a hipGraph. The library TRUSTS the
+ * offsets (it cannot read them without a synchronization) and clamps them: every offset into
+ * [0, text_off[B]] and a text's end to at least its start, so wrong offsets give wrong ids for that row,
+ * never an access outside text[0 .. text_off[B]). One wave per text; a row's output depends on neither B
+ * nor the row's position. Cost: linear in the text's bytes (DESIGN.md §4.12 states the bound). */
+int mec_tok_encode(mec_tokenizer* t, const uint8_t* text, const int64_t* text_off, int B, int L, int32_t* ids,
+                   int32_t* mask, int32_t* len, void* stream);
+int mec_tok_destroy(mec_tokenizer* t);
+
 /* ResNet50 image encoder + head. gray: u8[B,48,48]; the PIL RGB/resize/ToTensor/Normalize
  * transform runs on the GPU. Outputs feat f32[B,512] (fc[2]), logits, probs f32[B,7].
  * Replaces ImageInference.predict / extract_features (after Image.open)

@@ -3,8 +3,10 @@ Text inference (BERT-base sequence classification) on the MI355X HIP path — dr
 reference's inference/text_inference.py (same class, methods, result dicts, keyword fallback).
 
 The 12-layer encoder, pooler and classifier run as hand-written HIP kernels (csrc/bert.hip,
-csrc/gemm_glds.hip). Tokenisation stays on the host: a local BertTokenizer directory at
-Config.BERT_MODEL_PATH (never a hub download), exactly the reference's call at :78-85.
+csrc/gemm_glds.hip). Tokenisation: a local BertTokenizer directory at Config.BERT_MODEL_PATH (never a
+hub download), exactly the reference's call at :78-85, on the host by default; with tokenize='gpu' the
+batched calls tokenize in the HIP kernel of csrc/tokenizer.hip (engine.GpuTokenizer: the same ids and
+mask; texts that are not 7-bit or hold a special-token literal keep the host tokenizer, row by row).
 
 Added beyond the reference: predict_ids(ids, mask) for pre-tokenised input and
 predict_batch(ids, mask) for a device-resident [B,128] batch.
@@ -69,7 +71,9 @@ def encode_batch(tokenizer, texts):
 
 
 class TextInference:
-    def __init__(self, weights=None, seed=None, device=None, tokenizer=None, precision=None):
+    def __init__(self, weights=None, seed=None, device=None, tokenizer=None, precision=None, tokenize='host'):
+        if tokenize not in ('host', 'gpu'):
+            raise ValueError(f"tokenize must be 'host' or 'gpu', got {tokenize!r}")
         self.emotions = Config.EMOTIONS
         self.model = None
         self.preprocessor = _Cleaner()
@@ -79,6 +83,15 @@ class TextInference:
         self.tokenizer = tokenizer if tokenizer is not None else (_local_tokenizer() if self.model else None)
         self._fast = None  # built on first batched call
         self.device = self.model.device if self.model is not None else None
+        self.tokenize = tokenize
+        self.gpu_tokenizer = None
+        if tokenize == 'gpu':
+            if self.model is None or self.tokenizer is None:
+                raise ValueError("tokenize='gpu' needs the model and a tokenizer")
+            # its host rows come from the tokenizer the batched host path uses (the fast one when there is one)
+            self._host_fast()
+            self.gpu_tokenizer = engine.GpuTokenizer.from_bert(self._fast or self.tokenizer, device=self.device,
+                                                               max_length=Config.MAX_TEXT_LENGTH)
 
     def _keyword_heuristic(self, text: str) -> Dict:
         cleaned = self.preprocessor.clean_text(text)
@@ -138,29 +151,40 @@ class TextInference:
 
     def encode_batch(self, texts):
         """int32 ids / mask [B,128] for a list of strings (the fast tokenizer from the same
-        vocab when available: same ids as the reference's BertTokenizer, tests/test_tokenizer.py)."""
+        vocab when available: same ids as the reference's BertTokenizer, tests/test_tokenizer.py).
+        tokenize='gpu': the same integers as device tensors (engine.GpuTokenizer.encode)."""
+        if self.gpu_tokenizer is not None:
+            return self.gpu_tokenizer.encode(texts)[:2]
+        self._host_fast()
+        return encode_batch(self._fast or self.tokenizer, texts)
+
+    def _host_fast(self):
         if self._fast is None and self.tokenizer is not None and not getattr(self.tokenizer, 'is_fast', False):
             self._fast = _local_tokenizer(fast=True) or self.tokenizer
-        return encode_batch(self._fast or self.tokenizer, texts)
 
     def predict_texts(self, texts, pack: bool = False) -> List[Dict]:
         """Batched `predict`: one tokenizer call and one BERT forward for all texts.
 
         pack=True: short sentences share 128-token rows (engine.TextEncoder.forward_packed; the lengths
-        come from the tokenizer's mask on the host), so the encoder runs over fewer rows; the same
-        answers to the handle's rounding. Off by default: the padded path's outputs stay bit for bit."""
+        come from the tokenizer's mask on the host; tokenize='gpu': the kernel's B lengths are copied back),
+        so the encoder runs over fewer rows; the same answers to the handle's rounding. Off by default: the
+        padded path's outputs stay bit for bit."""
         texts = list(texts)
         if self.model is None or self.tokenizer is None:
             return [self._keyword_heuristic(t) for t in texts]
         if not texts:
             return []
-        ids, mask = self.encode_batch(texts)
-        if pack:
-            _, _, probs = self.model.checked('forward_packed', engine.to_device(ids, self.device),
-                                             engine.to_device(mask, self.device), mask.sum(1).astype(np.int32))
+        if self.gpu_tokenizer is not None:
+            ids, mask, n = self.gpu_tokenizer.encode(texts)
+            lens = n.cpu().numpy() if pack else None
         else:
-            _, _, probs = self.model.checked('forward', engine.to_device(ids, self.device),
-                                             engine.to_device(mask, self.device))
+            ids, mask = self.encode_batch(texts)
+            lens = mask.sum(1).astype(np.int32) if pack else None
+            ids, mask = engine.to_device(ids, self.device), engine.to_device(mask, self.device)
+        if pack:
+            _, _, probs = self.model.checked('forward_packed', ids, mask, lens)
+        else:
+            _, _, probs = self.model.checked('forward', ids, mask)
         probs = probs.cpu().numpy()
         return [self._as_dict(self.emotions, p) for p in probs]
 

@@ -4,9 +4,10 @@ inference/text_lstm_inference.py (same class, constructor, methods and result di
 
 The model arithmetic (Embedding -> two Bidirectional LSTMs -> three Dense layers -> softmax,
 model_training/train_lstm_text_model.py:96-120) runs in the HIP kernels of csrc/text_lstm.hip
-through libmec_hip.so; there is no CPU fallback. Tokenization stays on the host and restates
-Keras' Tokenizer.texts_to_sequences + pad_sequences(padding='post', truncating='post') as the
-reference calls them (:61-62, :101-102).
+through libmec_hip.so; there is no CPU fallback. Tokenization restates Keras'
+Tokenizer.texts_to_sequences + pad_sequences(padding='post', truncating='post') as the reference
+calls them (:61-62, :101-102): on the host by default (tokenize='host'), or in the HIP kernel of
+csrc/tokenizer.hip (tokenize='gpu', engine.GpuTokenizer: the same ids, so the same probabilities bit for bit).
 
 The reference unpickles its tokenizer (`_tokenizer.pkl`). This module never unpickles anything:
 it reads the word index from JSON, either Keras' own `tokenizer.to_json()` or a plain
@@ -40,7 +41,7 @@ class KerasWordIndex:
         self.word_index = {str(k): int(v) for k, v in word_index.items()}
         self.num_words = int(num_words) if num_words else None
         self.oov_index = self.word_index.get(oov_token) if oov_token is not None else None
-        self.lower, self.split = bool(lower), split
+        self.lower, self.split, self.filters = bool(lower), split, filters
         self._table = str.maketrans({c: split for c in filters})
 
     @classmethod
@@ -90,9 +91,14 @@ class FastTextEmotionPredictor:
 
     model_path: the reference's .h5 path (its converted text_lstm_weights.npz is read from the same
     directory) or the .npz itself; tokenizer_path: the tokenizer JSON. Added beyond the reference:
-    weights / seed / device / word_index (a {word: index} dict instead of a tokenizer file)."""
+    weights / seed / device / word_index (a {word: index} dict instead of a tokenizer file) / tokenize
+    ('host', the default: KerasWordIndex.padded; 'gpu': the ids are computed on the device, ValueError
+    when the tokenizer's split / filters are not single ASCII characters)."""
 
-    def __init__(self, model_path=None, tokenizer_path=None, weights=None, seed=None, device=None, word_index=None):
+    def __init__(self, model_path=None, tokenizer_path=None, weights=None, seed=None, device=None, word_index=None,
+                 tokenize='host'):
+        if tokenize not in ('host', 'gpu'):
+            raise ValueError(f"tokenize must be 'host' or 'gpu', got {tokenize!r}")
         self.model_path = model_path or Config.TEXT_MODEL_PATH
         self.tokenizer_path = tokenizer_path or checkpoints.lstm_tokenizer_path()
         if weights is None and seed is None and model_path is not None:
@@ -110,12 +116,18 @@ class FastTextEmotionPredictor:
             self.tokenizer_path)
         self.emotions = Config.EMOTIONS
         self.max_length = Config.MAX_TEXT_LENGTH
+        self.tokenize = tokenize
+        self.gpu_tokenizer = engine.GpuTokenizer.from_keras(
+            self.tokenizer, device=self.device, max_length=self.max_length) if tokenize == 'gpu' else None
 
     def _forward(self, texts):
         """-> (probs [n,7] numpy, milliseconds around the synchronized forward)."""
         import torch
-        padded = self.tokenizer.padded([t.lower().strip() for t in texts], self.max_length)
-        ids = engine.to_device(padded, self.device)
+        texts = [t.lower().strip() for t in texts]
+        if self.gpu_tokenizer is not None:
+            ids = self.gpu_tokenizer.encode(texts)[0]
+        else:
+            ids = engine.to_device(self.tokenizer.padded(texts, self.max_length), self.device)
         torch.cuda.synchronize(self.device)
         start = time.time()
         _, _, probs = self.model.forward(ids)

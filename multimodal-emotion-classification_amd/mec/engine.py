@@ -13,7 +13,7 @@ import threading
 import numpy as np
 import torch
 
-from . import _lib, synthetic
+from . import _lib, synthetic, tokenize as _tok
 from ._lib import MecError
 
 TAG_BERT_FFN2 = 5  # launch class of BERT's FFN2 GEMM (mec_common.h Tag)
@@ -338,6 +338,94 @@ class LstmTextEncoder(HipModel):
             _lib.check(self.lib.mec_text_lstm_fwd(self.handle, _ptr(ids), B, L, _ptr(feat), _ptr(logits), _ptr(probs),
                                                   _stream(self.device)), 'mec_text_lstm_fwd')
         return feat, logits, probs
+
+
+
+class GpuTokenizer:
+    """Tokenization on the GPU (mec_tok_*; csrc/tokenizer.hip): strings in, ids / mask / len on the device.
+
+    from_keras(word_index_obj) restates KerasWordIndex.padded, from_bert(tokenizer) the BERT tokenizer
+    call of inference/text_inference.py (add_special_tokens, max_length, padding='max_length',
+    truncation); both give exactly the host tokenizer's integers. A text the kernel's byte-level
+    specification does not cover (mec.tokenize: WORDPIECE, a text that is not 7-bit or holds a special-token
+    literal; either kind, a text without a UTF-8 encoding) is tokenized by `host_rows` and its row written
+    into the device result at its index, so the output order is the input order."""
+
+    def __init__(self, table: _tok.Table, host_rows, on_host=None, prepare=None, device=None, max_length: int = 128):
+        self.lib = _lib.load()
+        self.device = require_gpu(device)
+        self.table, self.L = table, int(max_length)
+        self._host_rows, self._on_host, self._prepare = host_rows, on_host, prepare
+        self.host_rows = 0  # rows the host tokenized in the last encode
+        desc, keep = table.desc()
+        h = ctypes.c_void_p()
+        torch.cuda.set_device(self.device)
+        self.handle = None
+        _lib.check(self.lib.mec_tok_create(ctypes.byref(desc), self.device.index, ctypes.byref(h)), 'mec_tok_create')
+        del keep
+        self.handle = h
+
+    @classmethod
+    def from_keras(cls, wi, device=None, max_length: int = 128):
+        """wi: a fitted word index (inference.text_lstm_inference.KerasWordIndex). ValueError when its
+        split / filters are not single ASCII characters."""
+        def host_rows(texts):
+            seqs = [wi.sequence(t)[:max_length] for t in texts]
+            ids = np.zeros((len(texts), max_length), np.int32)
+            for r, s in enumerate(seqs):
+                ids[r, :len(s)] = s
+            n = np.array([len(s) for s in seqs], np.int32)
+            return ids, (np.arange(max_length)[None, :] < n[:, None]).astype(np.int32), n
+        return cls(_tok.keras_table(wi), host_rows, None, (str.lower if wi.lower else None), device, max_length)
+
+    @classmethod
+    def from_bert(cls, tokenizer, device=None, max_length: int = 128):
+        """tokenizer: a transformers BertTokenizer / BertTokenizerFast. ValueError when it has added tokens
+        beyond its special tokens or strip_accents contradicts do_lower_case."""
+        def host_rows(texts):
+            enc = tokenizer(list(texts), add_special_tokens=True, max_length=max_length, padding='max_length',
+                            truncation=True, return_tensors='np')
+            mask = enc['attention_mask'].astype(np.int32)
+            return enc['input_ids'].astype(np.int32), mask, mask.sum(1).astype(np.int32)
+        return cls(_tok.wordpiece_table(tokenizer), host_rows, _tok.wordpiece_on_host(tokenizer.all_special_tokens),
+                   None, device, max_length)
+
+    def close(self):
+        if getattr(self, 'handle', None):
+            self.lib.mec_tok_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def encode(self, texts):
+        """texts: a list of str -> (ids int32 [B,L], mask int32 [B,L], len int32 [B]) on the device,
+        asynchronous on the current stream: one upload each for the bytes and the offsets, one kernel, and,
+        only when rows were routed to the host, one upload of those rows."""
+        texts = list(texts)
+        if self._prepare is not None:
+            texts = [self._prepare(t) for t in texts]
+        B, L = len(texts), self.L
+        blob, off, host = _tok.pack_texts(texts, self._on_host)
+        self.host_rows = len(host)
+        ids = torch.empty((B, L), dtype=torch.int32, device=self.device)
+        mask, n = torch.empty_like(ids), torch.empty((B,), dtype=torch.int32, device=self.device)
+        if B == 0:
+            return ids, mask, n
+        text_d, off_d = to_device(blob, self.device), to_device(off, self.device)
+        _lib.check(self.lib.mec_tok_encode(self.handle, _ptr(text_d), _ptr(off_d), B, L, _ptr(ids), _ptr(mask), _ptr(n),
+                                           _stream(self.device)), 'mec_tok_encode')
+        if host:
+            h_ids, h_mask, h_n = self._host_rows([texts[i] for i in host])
+            rows = torch.from_numpy(np.concatenate([h_ids, h_mask, h_n[:, None]], 1).astype(np.int32)).to(self.device)
+            at = torch.tensor(host, dtype=torch.int64, device=self.device)
+            ids.index_copy_(0, at, rows[:, :L])
+            mask.index_copy_(0, at, rows[:, L:2 * L])
+            n.index_copy_(0, at, rows[:, 2 * L])
+        return ids, mask, n
 
 
 class ImageEncoder(HipModel):
