@@ -315,6 +315,49 @@ typedef struct mec_gemm_args {
 } mec_gemm_args;
 int mec_gemm_ex(const mec_gemm_args* a, void* stream);
 
+/* Descriptor form of BERT's self-attention kernels: ctx = softmax(Q K^T / 8 + bias) V for `rows` sequences of
+ * 128 tokens x 12 heads of 64, through the launchers the text forwards use (every form they launch, nothing else).
+ *   precision  MEC_PREC_F16: f16 tensors. MEC_PREC_FP32: f32 tensors. MEC_PREC_FP32X3: f16 hi planes, each with
+ *              its lo plane `*_lo` elements further on, or paired ([rows][2K], mec_gemm_f16x3_paired's layout)
+ *              where `*_lo` is -1. ctx has the tensors' type (fp32x3: planes at ctx_lo, or paired).
+ *   form       0: all 128 queries; ctx [rows*128, 768]. 1: the [CLS] query only: qkv holds K | V
+ *              [rows*128, 1536], qc the queries [ns, 768], ctx [ns, 768] compact; sample b reads the K / V of
+ *              row b (ns == rows), or with `packed` those of row cidx[b] >> 7, its query sitting in slot
+ *              cidx[b] & 127 (cidx int32[ns], each in [0, rows*128): the library TRUSTS it).
+ *   fused      0: qkv holds Q | K | V [rows*128, 2304] (form 0). 1 (f16 and fp32x3, form 0 only): the QKV
+ *              projection in the same kernel, Q|K|V = (hs[rows*128, 768] . wqkv[2304, 768]^T) oscale + bqkv
+ *              (f16: oscale must be 1; fp32x3: hs and wqkv planar or paired together, and the K-interleaved
+ *              term order "gemm_x3_order" 1). Follows the process options bert_qkv_attn_heads /
+ *              bert_qkv_attn_x3_heads and qkv_x3_late_dma. The fp32x3 form raises the range flag of the
+ *              calling handle where mec_gemm_ex's split outputs do (none for this handle-less call).
+ *   packed     0: mask int32[rows, 128], a key counts where it is nonzero. 1: mask uint8[rows, 128] segment
+ *              ids, a key counts for the queries of its own segment.
+ *   qks        fp32x3: the factor on the raw scores, 1/8 2^-(s_q + s_k) for Q, K planes of q 2^s_q, k 2^s_k
+ *              (ctx carries V's scale); f16 / fp32: must be 0.125.
+ * A row without a valid key attends uniformly to all 128 keys (finfo(f32).min absorbs every finite score, as
+ * in transformers). rows (or ns) == 0 returns 0 without a launch; anything no kernel serves returns -1 before
+ * any launch. */
+typedef struct mec_attn_args {
+  int precision, form, fused, packed;
+  const void* qkv;
+  long long qkv_lo;
+  const void* qc;
+  long long qc_lo;
+  const void* hs;
+  long long hs_lo;
+  const void* wqkv;
+  long long w_lo;
+  const float* bqkv;
+  float oscale;
+  const void* mask;
+  const int32_t* cidx;
+  void* ctx;
+  long long ctx_lo;
+  float qks;
+  int rows, ns;
+} mec_attn_args;
+int mec_bert_attn(const mec_attn_args* a, void* stream);
+
 /* Tuning knobs (A/B benchmarking; defaults in brackets). Every handle owns its own copy of
  * the knobs and its own GEMM autotune cache, so two handles in one process never perturb
  * each other: mec_model_set_option sets one handle's knob; mec_set_option sets the process

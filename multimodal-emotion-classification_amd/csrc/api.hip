@@ -395,6 +395,79 @@ int mec_gemm_ex(const mec_gemm_args* a, void* stream) {
   })
 }
 
+int mec_bert_attn(const mec_attn_args* a, void* stream) {
+  API_GUARD({
+    MEC_REQUIRE(a, "mec_bert_attn: null descriptor");
+    const bool x3 = a->precision == MEC_PREC_FP32X3;
+    MEC_REQUIRE(a->precision == MEC_PREC_F16 || a->precision == MEC_PREC_FP32 || x3,
+                "mec_bert_attn: precision must be MEC_PREC_F16, MEC_PREC_FP32 or MEC_PREC_FP32X3");
+    MEC_REQUIRE((a->form == 0 || a->form == 1) && (a->fused == 0 || a->fused == 1) && (a->packed == 0 || a->packed == 1),
+                "mec_bert_attn: form, fused and packed are 0 or 1");
+    MEC_REQUIRE(a->rows >= 0 && a->rows <= (1 << 20), "mec_bert_attn: rows out of range");
+    MEC_REQUIRE(a->mask && a->ctx, "mec_bert_attn: null mask or ctx");
+    // a split tensor's lo plane: a positive element offset (16-B loads: a multiple of 8), or kX3Paired
+    auto lo_ok = [](long long lo) { return lo == kX3Paired || (lo > 0 && lo % 8 == 0); };
+    if (x3) {
+      MEC_REQUIRE(lo_ok(a->ctx_lo), "mec_bert_attn: ctx_lo must locate the lo plane (a multiple of 8) or be -1 (paired)");
+      MEC_REQUIRE(a->qks > 0.f && a->qks < 1e30f, "mec_bert_attn: qks must be set (1/8 2^-(s_q + s_k))");
+    } else {
+      MEC_REQUIRE(a->qks == 0.125f, "mec_bert_attn: the f16 and fp32 kernels scale the scores by 1/8 (qks = 0.125)");
+    }
+    const int32_t* mask = reinterpret_cast<const int32_t*>(a->mask);
+    if (a->fused) {
+      MEC_REQUIRE(a->precision != MEC_PREC_FP32, "mec_bert_attn: the fp32 path has no fused QKV + attention kernel");
+      MEC_REQUIRE(a->form == 0, "mec_bert_attn: the fused kernels serve all 128 queries only (form 0)");
+      MEC_REQUIRE(a->hs && a->wqkv && a->bqkv, "mec_bert_attn: fused needs hs, wqkv and bqkv");
+      if (a->rows == 0) return 0;
+      if (!x3) {
+        MEC_REQUIRE(a->oscale == 1.f, "mec_bert_attn: the f16 fused kernel has no output scale (oscale = 1)");
+        return launch_bert_qkv_attn(reinterpret_cast<const f16*>(a->hs), reinterpret_cast<const f16*>(a->wqkv), a->bqkv,
+                                    mask, reinterpret_cast<f16*>(a->ctx), a->rows, S(stream), a->packed != 0);
+      }
+      MEC_REQUIRE(lo_ok(a->hs_lo) && lo_ok(a->w_lo), "mec_bert_attn: hs_lo and w_lo must locate the lo planes or be -1");
+      MEC_REQUIRE(a->oscale > 0.f && a->oscale < 1e30f, "mec_bert_attn: oscale must be set (1 = none)");
+      MEC_REQUIRE(opt().gemm_x3_order == 1, "mec_bert_attn: the fused fp32x3 kernel has the K-interleaved term order (gemm_x3_order 1)");
+      return launch_bert_qkv_attn_x3(reinterpret_cast<const f16*>(a->hs), a->hs_lo, reinterpret_cast<const f16*>(a->wqkv),
+                                     a->w_lo, a->oscale, a->bqkv, mask, reinterpret_cast<f16*>(a->ctx), a->ctx_lo, a->rows,
+                                     a->qks, S(stream), a->packed != 0);
+    }
+    MEC_REQUIRE(a->qkv, "mec_bert_attn: null qkv");
+    MEC_REQUIRE(!x3 || lo_ok(a->qkv_lo), "mec_bert_attn: qkv_lo must locate the lo plane (a multiple of 8) or be -1 (paired)");
+    if (a->form == 0) {
+      if (a->rows == 0) return 0;
+      if (x3)
+        return launch_bert_attention_x3(reinterpret_cast<const f16*>(a->qkv), a->qkv_lo, mask, reinterpret_cast<f16*>(a->ctx),
+                                        a->ctx_lo, a->rows, a->qks, S(stream), a->packed != 0);
+      if (a->precision == MEC_PREC_FP32)
+        return launch_bert_attention_f32(reinterpret_cast<const float*>(a->qkv), mask, reinterpret_cast<float*>(a->ctx),
+                                         a->rows, S(stream), a->packed != 0);
+      return launch_bert_attention(reinterpret_cast<const f16*>(a->qkv), mask, reinterpret_cast<f16*>(a->ctx), a->rows,
+                                   S(stream), a->packed != 0);
+    }
+    // the [CLS]-only form: ns samples over `rows` rows of K | V
+    MEC_REQUIRE(a->qc, "mec_bert_attn: the [CLS]-only form needs qc");
+    MEC_REQUIRE(!x3 || lo_ok(a->qc_lo), "mec_bert_attn: qc_lo must locate the lo plane (a multiple of 8) or be -1 (paired)");
+    MEC_REQUIRE(a->ns >= 0 && a->ns <= (1 << 20), "mec_bert_attn: ns out of range");
+    if (a->packed) {
+      MEC_REQUIRE(a->cidx, "mec_bert_attn: the packed [CLS]-only form needs cidx");
+      MEC_REQUIRE(a->ns == 0 || a->rows >= 1, "mec_bert_attn: samples without a row");
+    } else {
+      MEC_REQUIRE(!a->cidx, "mec_bert_attn: cidx goes with packed");
+      MEC_REQUIRE(a->ns == a->rows, "mec_bert_attn: unpacked, sample b reads row b (ns == rows)");
+    }
+    if (a->ns == 0) return 0;
+    if (x3)
+      return launch_bert_attention_x3_cls(reinterpret_cast<const f16*>(a->qkv), a->qkv_lo, mask,
+                                          reinterpret_cast<const f16*>(a->qc), a->qc_lo, reinterpret_cast<f16*>(a->ctx),
+                                          a->ctx_lo, a->ns, a->qks, S(stream), a->cidx);
+    if (a->precision == MEC_PREC_FP32)
+      return launch_bert_attention_f32_cls(reinterpret_cast<const float*>(a->qkv), mask, reinterpret_cast<const float*>(a->qc),
+                                           reinterpret_cast<float*>(a->ctx), a->ns, S(stream), a->cidx);
+    return launch_bert_attention_cls(reinterpret_cast<const f16*>(a->qkv), mask, reinterpret_cast<const f16*>(a->qc),
+                                     reinterpret_cast<f16*>(a->ctx), a->ns, S(stream), a->cidx);
+  })
+}
+
 }  // extern "C"
 
 namespace mec {

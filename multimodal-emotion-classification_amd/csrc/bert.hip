@@ -1086,8 +1086,8 @@ int launch_bert_qkv_attn_x3(const f16* hs, long long hlo, const f16* wqkv, long 
 // ----------------------------------------------------------------------------- f16 attention launchers
 // kv: K | V of every token [rows * 128, 1536]; qc, ctx: the samples' [CLS] query / context rows [NS, 768];
 // cidx (or null): the packed form (mask = segment ids, sample b's [CLS] slot cidx[b])
-static int launch_bert_attention_cls(const f16* kv, const int32_t* mask, const f16* qc, f16* ctx, int NS, hipStream_t s,
-                                     const int32_t* cidx) {
+int launch_bert_attention_cls(const f16* kv, const int32_t* mask, const f16* qc, f16* ctx, int NS, hipStream_t s,
+                              const int32_t* cidx) {
   if (cidx)
     hipLaunchKernelGGL(bert_attention_cls_kernel<1>, dim3(NS * BHEADS), dim3(256), 0, s, kv, mask, qc, ctx, cidx);
   else
@@ -1097,8 +1097,8 @@ static int launch_bert_attention_cls(const f16* kv, const int32_t* mask, const f
 }
 
 // packed: mask holds the rows' uint8 segment ids and B counts packed rows (both launchers below)
-static int launch_bert_qkv_attn(const f16* h16, const f16* wqkv, const float* bqkv, const int32_t* mask, f16* ctx, int B,
-                                hipStream_t s, bool packed) {
+int launch_bert_qkv_attn(const f16* h16, const f16* wqkv, const float* bqkv, const int32_t* mask, f16* ctx, int B,
+                         hipStream_t s, bool packed) {
 #ifdef MEC_PROBES
   if (opt().bert_qkv_attn == 2)
     hipLaunchKernelGGL((bert_qkv_attn_kernel<1>), dim3(B * 6), dim3(512), 0, s, h16, wqkv, bqkv, mask, ctx, B);
@@ -1118,7 +1118,7 @@ static int launch_bert_qkv_attn(const f16* h16, const f16* wqkv, const float* bq
   return 0;
 }
 
-static int launch_bert_attention(const f16* qkv, const int32_t* mask, f16* ctx, int B, hipStream_t s, bool packed) {
+int launch_bert_attention(const f16* qkv, const int32_t* mask, f16* ctx, int B, hipStream_t s, bool packed) {
   if (packed)
     hipLaunchKernelGGL(bert_attention_kernel<1>, dim3(B * BHEADS), dim3(256), 0, s, qkv, mask, ctx);
   else

@@ -155,8 +155,8 @@ __global__ __launch_bounds__(256, 2) void bert_attention_f32_kernel(const float*
 
 // kv: K | V of every token [rows * 128, 1536]; qc, ctx: the samples' [CLS] query / context rows [NS, 768];
 // cidx (or null): the packed form (mask = segment ids, sample b's [CLS] slot cidx[b])
-static int launch_bert_attention_f32_cls(const float* kv, const int32_t* mask, const float* qc, float* ctx, int NS,
-                                         hipStream_t s, const int32_t* cidx) {
+int launch_bert_attention_f32_cls(const float* kv, const int32_t* mask, const float* qc, float* ctx, int NS,
+                                  hipStream_t s, const int32_t* cidx) {
   if (cidx)
     hipLaunchKernelGGL((bert_attention_f32_kernel<0, 1, 1>), dim3(NS * BHEADS), dim3(256), 0, s, kv, mask, ctx, nullptr,
                        0LL, qc, cidx);
@@ -168,8 +168,7 @@ static int launch_bert_attention_f32_cls(const float* kv, const int32_t* mask, c
 }
 
 // packed: mask holds the rows' uint8 segment ids and B counts packed rows
-static int launch_bert_attention_f32(const float* qkv, const int32_t* mask, float* ctx, int B, hipStream_t s,
-                                     bool packed) {
+int launch_bert_attention_f32(const float* qkv, const int32_t* mask, float* ctx, int B, hipStream_t s, bool packed) {
   if (packed)
     hipLaunchKernelGGL((bert_attention_f32_kernel<0, 0, 1>), dim3(B * BHEADS), dim3(256), 0, s, qkv, mask, ctx, nullptr,
                        0LL, nullptr, nullptr);

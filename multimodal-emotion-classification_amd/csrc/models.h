@@ -146,6 +146,18 @@ int launch_bert_embed_ln(const int32_t* ids, int M, int L, const float* emb, flo
                          long long lo = 0, float up = 1.f, const int32_t* posid = nullptr);
 int launch_bert_layernorm(const float* x, int M, const float* g, const float* b, float* h32, f16* h16, float2* stats,
                           hipStream_t s, long long lo = 0, float up = 1.f);
+// f16 attention (bert.hip): Q|K|V [B*128, 2304] -> ctx [B*128, 768]; its [CLS]-only form (K | V [rows*128,
+// 1536], the [CLS] queries qc and contexts ctx [NS, 768]; cidx or null as below); and the fused QKV
+// projection + attention (h16 [B*128, 768], wqkv [2304, 768]). fp32 attention (bert_f32.hip): the same two
+// unfused forms on f32 tensors. packed: mask holds the rows' uint8 segment ids and B counts packed rows
+int launch_bert_attention(const f16* qkv, const int32_t* mask, f16* ctx, int B, hipStream_t s, bool packed);
+int launch_bert_attention_cls(const f16* kv, const int32_t* mask, const f16* qc, f16* ctx, int NS, hipStream_t s,
+                              const int32_t* cidx);
+int launch_bert_qkv_attn(const f16* h16, const f16* wqkv, const float* bqkv, const int32_t* mask, f16* ctx, int B,
+                         hipStream_t s, bool packed);
+int launch_bert_attention_f32(const float* qkv, const int32_t* mask, float* ctx, int B, hipStream_t s, bool packed);
+int launch_bert_attention_f32_cls(const float* kv, const int32_t* mask, const float* qc, float* ctx, int NS,
+                                  hipStream_t s, const int32_t* cidx);
 // fp32x3 attention (bert.hip): Q|K|V as f16 hi / lo planes [B*128, 2304] (lo at qkv + lo) of q 2^s_q,
 // k 2^s_k, v 2^s_v; ctx 2^s_v written as hi / lo planes [B*128, 768] (lo at ctx + clo); qks = 1/8
 // 2^-(s_q + s_k) (the scores' scale)

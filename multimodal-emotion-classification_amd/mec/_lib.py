@@ -37,6 +37,23 @@ class GemmArgs(ctypes.Structure):
 
 A_PLAIN, A_CONV, A_DUAL = 0, 1, 2
 
+
+class AttnArgs(ctypes.Structure):
+    """include/mec.h mec_attn_args (mec_bert_attn's descriptor), field for field. qks defaults to 1/8 and
+    oscale to 1; a `*_lo` of X3_PAIRED says that split tensor is paired."""
+    _fields_ = [('precision', c_int), ('form', c_int), ('fused', c_int), ('packed', c_int),
+                ('qkv', c_vp), ('qkv_lo', ctypes.c_longlong), ('qc', c_vp), ('qc_lo', ctypes.c_longlong),
+                ('hs', c_vp), ('hs_lo', ctypes.c_longlong), ('wqkv', c_vp), ('w_lo', ctypes.c_longlong),
+                ('bqkv', c_vp), ('oscale', ctypes.c_float), ('mask', c_vp), ('cidx', c_vp),
+                ('ctx', c_vp), ('ctx_lo', ctypes.c_longlong), ('qks', ctypes.c_float),
+                ('rows', c_int), ('ns', c_int)]
+
+    def __init__(self, **kw):
+        super().__init__(**{'oscale': 1.0, 'qks': 0.125, **kw})
+
+
+X3_PAIRED = -1
+
 # name -> (restype, argtypes); mirrors include/mec.h one to one.
 SIGNATURES = {
     'mec_version': (ctypes.c_char_p, []),
@@ -76,6 +93,7 @@ SIGNATURES = {
     'mec_conv_f32': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                              c_int, c_int, c_vp]),
     'mec_gemm_ex': (c_int, [ctypes.POINTER(GemmArgs), c_vp]),
+    'mec_bert_attn': (c_int, [ctypes.POINTER(AttnArgs), c_vp]),
     'mec_set_option': (c_int, [ctypes.c_char_p, c_int]),
     'mec_model_set_option': (c_int, [c_vp, ctypes.c_char_p, c_int]),
     'mec_build_flags': (c_int, []),

@@ -18,17 +18,19 @@ import torch.nn.functional as F
 H, HEADS, DH, LAYERS = 768, 12, 64, 12
 
 
-def _t(a):
-    return torch.from_numpy(np.asarray(a, np.float32))
+def _t(a, dtype=torch.float32):
+    return torch.from_numpy(np.asarray(a, np.float32)).to(dtype)
 
 
 @torch.no_grad()
-def forward(w, ids: np.ndarray, mask: np.ndarray):
-    """ids/mask int [B,L] -> (cls [B,768], logits [B,7], probs [B,7]) as float32 numpy."""
+def forward(w, ids: np.ndarray, mask: np.ndarray, dtype=torch.float32):
+    """ids/mask int [B,L] -> (cls [B,768], logits [B,7], probs [B,7]) as numpy arrays of `dtype`: float32, the
+    reference's arithmetic, or float64, the same forward on the same fp32 weights for measuring the float32
+    one's own error (the mask term stays finfo(float32).min, which absorbs every finite score in both)."""
     ids_t = torch.from_numpy(np.asarray(ids, np.int64))
-    m = torch.from_numpy(np.asarray(mask, np.float32))
+    m = torch.from_numpy(np.asarray(mask, np.float32)).to(dtype)
     B, L = ids_t.shape
-    g = lambda n: _t(w[n])
+    g = lambda n: _t(w[n], dtype)
     p = 'bert.embeddings.'
     x = F.embedding(ids_t, g(p + 'word_embeddings.weight')) + g(p + 'token_type_embeddings.weight')[0]
     x = x + g(p + 'position_embeddings.weight')[:L][None]

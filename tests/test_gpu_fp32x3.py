@@ -9,6 +9,7 @@ import torch
 
 from mec import engine, synthetic as syn
 from oracle import image as o_i, text as o_t
+from text_edits import edit as _edit
 
 pytestmark = pytest.mark.gpu
 
@@ -359,20 +360,6 @@ def test_split_gemm_small_activations_scaled_planes(dev, scale):
           f'split {(ex3 / aw).max():.3g} (unscaled planes {(eu / aw).max():.3g})')
     assert (e32 <= 2e-6 * aw + 1e-30).all()
     assert (ex3 <= 2e-6 * aw + 1e-30).all()
-
-
-def _edit(kind, edits):
-    """A copy of the seeded weights with edits {name: factor | (index, value)} applied (syn.weights
-    returns the cached dict every handle shares)."""
-    w = dict(syn.weights(kind))
-    for name, e in edits.items():
-        a = np.array(w[name], np.float32)
-        if isinstance(e, tuple):
-            a.flat[e[0]] = e[1]
-        else:
-            a = (a * np.float32(e)).astype(np.float32)
-        w[name] = a
-    return w
 
 
 def _raises_then_clears(enc):

@@ -157,6 +157,42 @@ def test_gemm_ex_descriptor_errors_without_gpu():
         assert msg in lib.mec_last_error(), (kw, lib.mec_last_error())
 
 
+def test_bert_attn_descriptor_errors_without_gpu():
+    """mec_bert_attn returns -1 and says why for every form no attention kernel serves; the checks precede
+    every device call (the fake pointers are never read), and an empty launch returns 0."""
+    import ctypes
+    lib = _lib.load()
+    p = ctypes.c_void_p(0x1000)
+    assert lib.mec_bert_attn(None, None) == -1 and b'null descriptor' in lib.mec_last_error()
+    F16, FP32, X3 = (_lib.PRECISIONS[n] for n in ('f16', 'fp32', 'fp32x3'))
+    full = dict(qkv=p, mask=p, ctx=p, rows=2)
+    x3 = dict(precision=X3, qkv_lo=4096, ctx_lo=4096)
+    fused = dict(fused=1, hs=p, wqkv=p, bqkv=p, mask=p, ctx=p, rows=2)
+    cls = dict(form=1, qkv=p, qc=p, mask=p, ctx=p, rows=2, ns=2)
+    for kw, msg in (({**full, 'precision': 3}, b'precision'), ({**full, 'form': 2}, b'form, fused and packed'),
+                    ({**full, 'packed': 2}, b'form, fused and packed'), ({**full, 'rows': -1}, b'rows'),
+                    ({**full, 'mask': None}, b'null mask or ctx'), ({**full, 'ctx': None}, b'null mask or ctx'),
+                    ({**full, 'qkv': None}, b'null qkv'), ({**full, 'qks': 0.25}, b'qks = 0.125'),
+                    ({**full, 'precision': FP32, 'qks': 0.5}, b'qks = 0.125'),
+                    ({**full, **x3, 'qks': 0.0}, b'qks must be set'), ({**full, **x3, 'ctx_lo': 0}, b'ctx_lo'),
+                    ({**full, **x3, 'qkv_lo': 0}, b'qkv_lo'), ({**full, **x3, 'qkv_lo': 4100}, b'qkv_lo'),
+                    ({**fused, 'precision': FP32}, b'no fused'), ({**fused, 'form': 1}, b'form 0'),
+                    ({**fused, 'bqkv': None}, b'hs, wqkv and bqkv'), ({**fused, 'oscale': 0.5}, b'oscale = 1'),
+                    ({**fused, **x3, 'hs_lo': 4096, 'w_lo': 0}, b'hs_lo and w_lo'),
+                    ({**fused, **x3, 'hs_lo': 4096, 'w_lo': -1}, b'paired together'),
+                    ({**fused, **x3, 'hs_lo': 4096, 'w_lo': 4096, 'oscale': 0.0}, b'oscale must be set'),
+                    ({**cls, 'qc': None}, b'needs qc'), ({**cls, 'ns': 3}, b'ns == rows'),
+                    ({**cls, 'cidx': p}, b'cidx goes with packed'), ({**cls, 'packed': 1}, b'needs cidx'),
+                    ({**cls, 'packed': 1, 'cidx': p, 'rows': 0}, b'samples without a row'),
+                    ({**cls, **x3, 'qc_lo': 0}, b'qc_lo'), ({**cls, 'ns': -1, 'rows': -1}, b'rows')):
+        a = _lib.AttnArgs(**kw)
+        assert lib.mec_bert_attn(ctypes.byref(a), None) == -1, kw
+        assert msg in lib.mec_last_error(), (kw, lib.mec_last_error())
+    for kw in ({**full, 'rows': 0}, {**fused, 'rows': 0}, {**cls, 'rows': 0, 'ns': 0},
+               {**cls, 'packed': 1, 'cidx': p, 'ns': 0}):
+        assert lib.mec_bert_attn(ctypes.byref(_lib.AttnArgs(**kw)), None) == 0, kw
+
+
 @pytest.mark.parametrize('geom', ['G1', 'G2', 'G3', 'G4', 'G5'])
 def test_gemm_mode_references_vs_torch_conv2d_f64(geom):
     """The float64 NHWC conv, tap-view and dual-gather helpers the GPU GEMM-mode tests compare kernels
