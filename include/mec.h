@@ -161,18 +161,38 @@ int mec_text_lstm_fwd(mec_model* m, const int32_t* ids, int B, int L, float* fea
  * than max_word is unk_id, else greedy longest-match-first, plain entries at word position 0 and, later in
  * the word, entries whose pool form starts with "##" (the prefix is stripped into a flag at creation); a
  * word with an unmatched position is one unk_id. The row is cls_id, the first L-2 pieces, sep_id, then
- * pad_id; len counts cls_id and sep_id, mask[j] = j < len. */
+ * pad_id; len counts cls_id and sep_id, mask[j] = j < len.
+ *
+ * MEC_TOK_WORDPIECE_UTF8 (mec_tok_create_utf8) is MEC_TOK_WORDPIECE for any well-formed UTF-8 text, for a
+ * lower-casing, accent-stripping BERT tokenizer, whose Unicode handling is one table look-up per code point
+ * (mec_tok_cpmap below). The text is decoded code point by code point. A code point below 0x80 follows the
+ * 7-bit rules above (`lower` included), so a 7-bit text gets the row MEC_TOK_WORDPIECE gives it. Any other
+ * code point acts by its class: DROP vanishes (its neighbours join); SPACE ends the word; CHAR appends the
+ * code point's own UTF-8 bytes to the word; PUNCT ends the word and is a word of its own; MAPPED stands for
+ * its 0 to 3 output code points in order, each of which is appended to the word or, when its own class is
+ * PUNCT (below 0x80: when it is a punctuation byte), ends the word and is a word of its own. With the
+ * ISOLATE flag the word ends before and after the code point, so that its output is a word of its own. A
+ * word that ends up empty emits nothing. max_word counts the word's output CHARACTERS, not bytes: a word of
+ * more is unk_id. Matching, cls_id, the first L-2 pieces, sep_id, pad_id, mask and len are as for
+ * MEC_TOK_WORDPIECE, on the word's bytes. The table holds every entry, which must be well-formed UTF-8.
+ * Byte-level matching never splits a character: a piece starts on a character boundary (the word's start,
+ * or the end of the piece before it), and from a boundary a well-formed entry can only equal whole
+ * characters, since each lead byte fixes its character's length; so it ends on a boundary too.
+ * A row whose text holds an UNCOVERED code point or ill-formed UTF-8 anywhere (an overlong form, a
+ * surrogate, a value above 0x10FFFF, a sequence cut off by the text's end, a stray continuation byte, a
+ * byte that no sequence holds) is pad_id throughout with mask 0 and len = -1: never a guess, and never an
+ * access outside the text. */
 typedef struct mec_tokenizer mec_tokenizer;
-enum { MEC_TOK_KERAS = 0, MEC_TOK_WORDPIECE = 1 };
+enum { MEC_TOK_KERAS = 0, MEC_TOK_WORDPIECE = 1, MEC_TOK_WORDPIECE_UTF8 = 2 };
 typedef struct mec_tok_desc {
-  int kind;             /* MEC_TOK_KERAS or MEC_TOK_WORDPIECE */
+  int kind;             /* MEC_TOK_KERAS, MEC_TOK_WORDPIECE or MEC_TOK_WORDPIECE_UTF8 */
   const uint8_t* pool;  /* HOST: the entries' bytes, back to back */
   const int64_t* off;   /* HOST: n + 1 monotone offsets into pool, off[0] >= 0 */
   const int32_t* id;    /* HOST: n ids, each >= 0 */
   int n;
   uint8_t delim[256];   /* KERAS: 1 = this byte separates words */
   int oov_id;           /* KERAS: id written for a word not in the table; -1 = such words are dropped */
-  int lower;            /* WORDPIECE: fold A-Z to a-z */
+  int lower;            /* WORDPIECE (both kinds from here on): fold A-Z to a-z */
   int unk_id, cls_id, sep_id, pad_id; /* WORDPIECE */
   int max_word;         /* WORDPIECE: 1..128 (transformers: 100) */
 } mec_tok_desc;
@@ -181,9 +201,31 @@ typedef struct mec_tok_desc {
  * holding a byte >= 0x80, a special id < 0 or max_word outside 1..128. Nothing of the descriptor is
  * referenced after the call returns. */
 int mec_tok_create(const mec_tok_desc* d, int device, mec_tokenizer** out);
+/* The code-point table of MEC_TOK_WORDPIECE_UTF8, HOST arrays. cls[cp] = a class in the low 3 bits, or'ed
+ * with MEC_CP_ISOLATE; entries 0..127 are ignored (the 7-bit rules hold there). The MAPPED code points are
+ * listed in map_cp, ascending, with the outputs of map_cp[i] at map_out[map_off[i] .. map_off[i+1]). */
+enum { MEC_CP_UNCOVERED = 0, MEC_CP_DROP = 1, MEC_CP_SPACE = 2, MEC_CP_CHAR = 3, MEC_CP_PUNCT = 4, MEC_CP_MAPPED = 5,
+       MEC_CP_ISOLATE = 8 };
+typedef struct mec_tok_cpmap {
+  const uint8_t* cls;     /* HOST: 0x110000 entries */
+  const int32_t* map_cp;  /* HOST: n_map code points >= 0x80, strictly ascending, exactly those of class MAPPED */
+  const int32_t* map_off; /* HOST: n_map + 1 offsets into map_out, map_off[0] = 0, 0..3 outputs each */
+  const int32_t* map_out; /* HOST: the outputs; each of class CHAR or PUNCT, or a 7-bit word character or
+                             punctuation byte (A-Z is folded when the descriptor's `lower` is set) */
+  int n_map;
+} mec_tok_cpmap;
+/* d->kind must be MEC_TOK_WORDPIECE_UTF8. Returns -1 for everything mec_tok_create rejects (an entry with a
+ * byte >= 0x80 is fine here, an entry that is not well-formed UTF-8 is not) and for a null pointer in m, a
+ * class above MAPPED, a surrogate or a value >= 0x110000 that is not UNCOVERED, a map_cp that is not
+ * strictly ascending, below 0x80 or not of class MAPPED, a MAPPED code point that map_cp lacks, more than 3
+ * outputs, and an output that is not of class CHAR or PUNCT (below 0x80: that the 7-bit rules drop or treat
+ * as whitespace). Creation folds cls and the map into a two-stage table (an index by cp >> 7 into shared
+ * 128-entry blocks, the outputs as UTF-8 bytes with their punctuation flags) and uploads it with the
+ * vocabulary table as one allocation. mec_tok_encode and mec_tok_destroy serve the tokenizer as any other. */
+int mec_tok_create_utf8(const mec_tok_desc* d, const mec_tok_cpmap* m, int device, mec_tokenizer** out);
 /* text u8 and text_off int64[B+1] are DEVICE pointers: text i is the bytes text[text_off[i] ..
  * text_off[i+1]), and text_off[B] is the blob's size. Outputs (device) ids int32[B,L], mask int32[B,L] or
- * NULL, len int32[B] or NULL; 1 <= L <= 512 (WORDPIECE: 2 <= L). B == 0 returns 0 without a launch; a null
+ * NULL, len int32[B] or NULL; 1 <= L <= 512 (both WORDPIECE kinds: 2 <= L). B == 0 returns 0 without a launch; a null
  * tokenizer, text, text_off or ids, B < 0 or L out of range return -1 before any launch. Asynchronous on
  * `stream`; allocates nothing, never synchronizes, can be captured into a hipGraph. The library TRUSTS the
  * offsets (it cannot read them without a synchronization) and clamps them: every offset into

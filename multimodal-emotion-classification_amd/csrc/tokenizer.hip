@@ -1,7 +1,7 @@
 // Tokenization on the GPU (include/mec.h mec_tok_*): UTF-8 bytes in, ids / mask / len out, for the
-// BiLSTM path (MEC_TOK_KERAS) and the BERT path (MEC_TOK_WORDPIECE). One wave per text. The
-// vocabulary is an open-addressing hash table built on the host (tok_table.h); every hash hit is
-// confirmed against the byte pool. All stores are ordinary vector stores.
+// BiLSTM path (MEC_TOK_KERAS) and the BERT path (MEC_TOK_WORDPIECE for 7-bit text, MEC_TOK_WORDPIECE_UTF8
+// for any text). One wave per text. The vocabulary is an open-addressing hash table built on the host
+// (tok_table.h); every hash hit is confirmed against the byte pool. All stores are ordinary vector stores.
 #include <algorithm>
 
 #include "mec.h"
@@ -18,6 +18,9 @@ struct Params {
   uint32_t mask;
   int max_len;
   int oov_id, lower, unk_id, cls_id, sep_id, pad_id, max_word;
+  const uint16_t* cp_index;  // WORDPIECE_UTF8: the code-point table (tok_table.h CpTable)
+  const uint32_t* cp_block;
+  const uint8_t* cp_exp;
 };
 
 __device__ inline uint64_t lanes_below(int lane) { return (1ull << lane) - 1ull; }
@@ -92,30 +95,49 @@ __global__ __launch_bounds__(64) void keras_kernel(Params p, const uint8_t* __re
 // a punctuation byte ends it and is a word of its own. A finished word is matched by the whole wave:
 // the lanes hold the word's prefix hashes, and for the current start the lanes test the candidate ends
 // in parallel, longest first, so one probe round finds the longest piece.
+//
+// WORDPIECE_UTF8 is the same kernel with a second walk for the chunks that hold a byte >= 0x80 (a chunk
+// without one takes the walk above). There the lanes at a character's first byte decode it, reading up to
+// 3 bytes past the chunk but never past the text, and look its class up in the two-stage table; a lane is
+// then whitespace, nothing (a continuation byte, a dropped character), a plain word character that stands
+// for nb bytes and nc characters (its own bytes, or a MAPPED character's outputs), or a "complex"
+// character (one with a punctuation output or the ISOLATE flag), which the walk handles one at a time as
+// it handles a punctuation byte. One wave scan of (nc, nb) per chunk places a stretch's bytes in the LDS
+// word. A word is at most max_word characters, so its buffers hold 4 * kWordCap bytes. The count of
+// continuation bytes that a chunk's last character leaves to the next chunk is carried like the word.
+template <int CAP>
 struct WordState {
-  uint8_t* word;     // LDS [kWordCap]
-  uint32_t* prefix;  // LDS [kWordCap + 1]: prefix hashes of the word
-  uint32_t* power;   // LDS [kWordCap + 1]: kP^k
-  int32_t* pieces;   // LDS [kWordCap]
+  uint8_t* word;     // LDS [CAP]
+  uint32_t* prefix;  // LDS [CAP + 1]: prefix hashes of the word
+  uint32_t* power;   // LDS [CAP + 1]: kP^k
+  int32_t* pieces;   // LDS [CAP]
 };
 
-// Tokenize the word of n bytes (the first min(n, kWordCap) are in ws.word) and write its pieces at
-// out[1 + np ...], as far as they are among the first `need`. Returns the number of pieces.
-__device__ inline int flush_word(const Params& p, const WordState& ws, int n, int np, int need, int32_t* out) {
+// Tokenize the word of n bytes and nch characters (the first min(n, CAP) bytes are in ws.word) and write
+// its pieces at out[1 + np ...], as far as they are among the first `need`. Returns the number of pieces.
+// nch <= max_word <= kWordCap implies n <= CAP: CAP is kWordCap times the longest character.
+template <int CAP>
+__device__ inline int flush_word(const Params& p, const WordState<CAP>& ws, int n, int nch, int np, int need,
+                                 int32_t* out) {
+  constexpr int NH = CAP / 64;  // prefix hashes per lane: lane's j-th is that of the first lane + 64 j + 1 bytes
   const int lane = threadIdx.x;
   __syncthreads();  // the word's bytes are in LDS
   int nw = 0;
-  bool bad = n > p.max_word;
+  bool bad = nch > p.max_word;
   if (!bad) {
-    uint32_t ha = 0, hb = 0;
+    uint32_t h[NH];
+#pragma unroll
+    for (int j = 0; j < NH; ++j) h[j] = 0;
     for (int i = 0; i < n; ++i) {
       const uint32_t c = ws.word[i];
-      if (i <= lane) ha = step(ha, c);
-      if (i <= lane + 64) hb = step(hb, c);
+#pragma unroll
+      for (int j = 0; j < NH; ++j)
+        if ((j < 2 || j * 64 < n) && i <= lane + 64 * j) h[j] = step(h[j], c);
     }
     if (lane == 0) ws.prefix[0] = 0;
-    if (lane + 1 <= n) ws.prefix[lane + 1] = ha;
-    if (lane + 65 <= n) ws.prefix[lane + 65] = hb;
+#pragma unroll
+    for (int j = 0; j < NH; ++j)
+      if (lane + 64 * j + 1 <= n) ws.prefix[lane + 64 * j + 1] = h[j];
     __syncthreads();
     int s = 0;
     while (s < n) {
@@ -158,39 +180,178 @@ __device__ inline int flush_word(const Params& p, const WordState& ws, int n, in
   return nw;
 }
 
+// What a lane of a chunk with a byte >= 0x80 stands for (WORDPIECE_UTF8).
+enum { kNone = 0, kSpace = 1, kChar = 2, kComplex = 3 };
+// A complex lane's outputs: count | punctuation flags << 2 | ISOLATE << 5 | byte length of output j << (6 + 3 j)
+constexpr int kCxPunct = 2, kCxIsolate = 5, kCxLen = 6;
+
+__device__ inline int utf8_len(uint32_t lead) { return lead < 0x80 ? 1 : lead < 0xE0 ? 2 : lead < 0xF0 ? 3 : 4; }
+
+template <bool UTF8>
 __global__ __launch_bounds__(64) void wordpiece_kernel(Params p, const uint8_t* __restrict__ text,
                                                        const int64_t* __restrict__ text_off, int B, int L,
                                                        int32_t* __restrict__ ids, int32_t* __restrict__ mask,
                                                        int32_t* __restrict__ len) {
-  __shared__ uint8_t s_word[kWordCap];
-  __shared__ uint32_t s_prefix[kWordCap + 1];
-  __shared__ uint32_t s_power[kWordCap + 1];
-  __shared__ int32_t s_pieces[kWordCap];
-  const WordState ws{s_word, s_prefix, s_power, s_pieces};
+  constexpr int CAP = UTF8 ? 4 * kWordCap : kWordCap;
+  __shared__ uint8_t s_word[CAP];
+  __shared__ uint32_t s_prefix[CAP + 1];
+  __shared__ uint32_t s_power[CAP + 1];
+  __shared__ int32_t s_pieces[CAP];
+  const WordState<CAP> ws{s_word, s_prefix, s_power, s_pieces};
   const int row = blockIdx.x, lane = threadIdx.x;
   {
     uint32_t pw = 1;
     for (int i = 0; i < lane; ++i) pw *= kP;
-    s_power[lane] = pw;
     uint32_t p64 = 1;
     for (int i = 0; i < 64; ++i) p64 *= kP;
-    s_power[lane + 64] = pw * p64;
-    if (lane == 0) s_power[128] = p64 * p64;
+    uint32_t hi = 1;
+    for (int j = 0; j < CAP / 64; ++j, hi *= p64) s_power[lane + 64 * j] = pw * hi;
+    if (lane == 0) s_power[CAP] = hi;
   }
   __syncthreads();
   int64_t beg, end;
   text_span(text_off, B, row, beg, end);
   int32_t* out = ids + (size_t)row * L;
   const int need = L - 2;
-  int np = 0;    // pieces so far (all words' counts; only the first `need` are written)
-  int wlen = 0;  // bytes of the word being collected (counted past kWordCap, stored up to it)
-  for (int64_t base = beg; base < end && np < need; base += 64) {
+  int np = 0;         // pieces so far (all words' counts; only the first `need` are written)
+  int wlen = 0;       // bytes of the word being collected (counted past CAP, stored up to it)
+  int wch = 0;        // its characters
+  int skip = 0;       // UTF8: continuation bytes at the next chunk's start that end this chunk's last character
+  bool bad = false;   // UTF8: the text is ill-formed or holds an uncovered code point
+  auto flush = [&]() {
+    np += flush_word(p, ws, wlen, wch, np, need, out);
+    wlen = wch = 0;
+  };
+  // UTF8 reads the whole text, also past the last piece that fits: the row's validity is the text's
+  for (int64_t base = beg; base < end && (UTF8 || np < need); base += 64) {
     const int64_t pos = base + lane;
     uint32_t b = pos < end ? text[pos] : ' ';
+    if (UTF8 && __ballot(b >= 0x80)) {
+      int kind = kNone, nb = 0, nc = 0, ab = -1, cx = 0, clen = 0;
+      const uint8_t* src = text + pos;  // the lane's output bytes, unless ab >= 0 is its one byte
+      bool ill = false, cont = false;
+      if (pos < end) {
+        if (b < 0x80) {
+          if (p.lower && b >= 'A' && b <= 'Z') b += 32;
+          ab = (int)b;
+          if (ascii_space(b)) kind = kSpace;
+          else if (ascii_punct(b)) kind = kComplex, cx = 1 | 1 << kCxPunct | 1 << kCxLen;
+          else if (!ascii_drop(b)) kind = kChar, nb = nc = 1;
+        } else if (b < 0xC0) {
+          cont = true;
+        } else {
+          clen = utf8_len(b);
+          ill = b < 0xC2 || b > 0xF4;
+          uint32_t cp = b & (0x7Fu >> clen);
+          for (int k = 1; k < clen; ++k) {
+            const uint32_t c = pos + k < end ? text[pos + k] : 0u;  // the text's end cuts the character off
+            ill |= (c & 0xC0) != 0x80;
+            cp = cp << 6 | (c & 0x3F);
+          }
+          ill |= cp < (clen == 2 ? 0x80u : clen == 3 ? 0x800u : 0x10000u) || (cp >= 0xD800 && cp <= 0xDFFF) || cp > 0x10FFFF;
+          if (!ill) {
+            const uint32_t e = cp_entry(p.cp_index, p.cp_block, cp);
+            const int c = e & 7, iso = (e & MEC_CP_ISOLATE) != 0;
+            if (c == MEC_CP_UNCOVERED) {
+              ill = true;
+            } else if (c == MEC_CP_SPACE) {
+              kind = kSpace;
+            } else if (c == MEC_CP_CHAR && !iso) {
+              kind = kChar, nb = clen, nc = 1;
+            } else if (c == MEC_CP_CHAR || c == MEC_CP_PUNCT) {
+              kind = kComplex, cx = 1 | (c == MEC_CP_PUNCT) << kCxPunct | iso << kCxIsolate | clen << kCxLen;
+            } else if (c == MEC_CP_MAPPED) {
+              const uint8_t* rec = p.cp_exp + (e >> kCpExpShift);
+              const int bytes = rec[0], k = rec[1] & 3, pm = rec[1] >> 2;
+              src = rec + 2;
+              if (k == 0) {
+                kind = iso ? kSpace : kNone;  // no output: it vanishes, or only separates
+              } else if (pm || iso) {
+                kind = kComplex, cx = k | pm << kCxPunct | iso << kCxIsolate;
+                for (int j = 0, o = 0; j < k; ++j) {
+                  const int l = utf8_len(src[o]);
+                  cx |= l << (kCxLen + 3 * j);
+                  o += l;
+                }
+              } else {
+                kind = kChar, nb = bytes, nc = k;
+              }
+            }
+          }
+        }
+      }
+      const uint64_t l2 = __ballot(clen == 2), l3 = __ballot(clen == 3), l4 = __ballot(clen == 4);
+      const uint64_t leads = l2 | l3 | l4;
+      const uint64_t held = leads << 1 | (l3 | l4) << 2 | l4 << 3 | lanes_below(skip);
+      bad = __ballot(ill) != 0 || (__ballot(cont) & ~held) != 0;
+      if (bad) break;
+      skip = 0;
+      if (leads) {
+        const int last = 63 - __clzll((long long)leads);
+        skip = max(last + ((l2 >> last) & 1 ? 2 : (l3 >> last) & 1 ? 3 : 4) - 64, 0);
+      }
+      if (np >= need) continue;
+      const uint64_t chm = __ballot(kind == kChar), cxm = __ballot(kind == kComplex), spm = __ballot(kind == kSpace);
+      // inclusive wave scan of characters << 16 | bytes over the plain word characters
+      const int own = kind == kChar ? nc << 16 | nb : 0;
+      int inc = own;
+      for (int d = 1; d < 64; d <<= 1) {
+        const int up = __shfl_up(inc, d);
+        if (lane >= d) inc += up;
+      }
+      const int exc = inc - own;
+      auto put = [&](int at, int from, int n) {  // this lane's output bytes [from, from + n) to word[at ...]
+        for (int k = 0; k < n; ++k)
+          if (at + k < CAP) s_word[at + k] = ab >= 0 ? (uint8_t)ab : src[from + k];
+      };
+      uint64_t rem = chm | cxm | spm;
+      while (rem && np < need) {
+        const int first = __ffsll((unsigned long long)rem) - 1;
+        if ((chm >> first) & 1) {
+          const uint64_t stop = rem & ~chm;
+          const int q = stop ? __ffsll((unsigned long long)stop) - 1 : 64;
+          const uint64_t below_q = q == 64 ? ~0ull : lanes_below(q);
+          const int from = __shfl(exc, first);
+          const int sum = (q == 64 ? __shfl(inc, 63) : __shfl(exc, q)) - from;
+          if (((rem & below_q) >> lane) & 1) put(wlen + ((exc - from) & 0xFFFF), 0, nb);
+          wlen = min(wlen + (sum & 0xFFFF), 1 << 20);
+          wch = min(wch + (sum >> 16), 1 << 20);
+          rem &= ~below_q;
+          if (q < 64) flush();
+        } else if ((spm >> first) & 1) {
+          if (wlen) flush();
+          const uint64_t next = rem & ~spm;
+          rem = next ? rem & ~lanes_below(__ffsll((unsigned long long)next) - 1) : 0;
+        } else {
+          const int d = __shfl(cx, first);
+          const int iso = (d >> kCxIsolate) & 1;
+          if (iso && wlen) flush();
+          for (int j = 0, o = 0; j < (d & 3) && np < need; ++j) {
+            const int l = (d >> (kCxLen + 3 * j)) & 7;
+            if ((d >> (kCxPunct + j)) & 1) {
+              if (wlen) flush();
+              if (np < need) {
+                if (lane == first) put(0, o, l);
+                wlen = l, wch = 1;
+                flush();
+              }
+            } else {
+              if (lane == first) put(wlen, o, l);
+              wlen = min(wlen + l, 1 << 20);
+              wch = min(wch + 1, 1 << 20);
+            }
+            o += l;
+          }
+          if (iso && wlen && np < need) flush();
+          rem &= rem - 1;
+        }
+      }
+      continue;
+    }
+    skip = 0;  // a character that this chunk cuts off was found ill-formed by its first byte's lane
+    if (UTF8 && np >= need) continue;
     if (p.lower && b >= 'A' && b <= 'Z') b += 32;
-    const bool space = b == ' ' || b == '\t' || b == '\n' || b == '\r';
-    const bool drop = !space && (b < 0x20 || b == 0x7F);
-    const bool punct = (b >= 33 && b <= 47) || (b >= 58 && b <= 64) || (b >= 91 && b <= 96) || (b >= 123 && b <= 126);
+    const bool space = ascii_space(b), drop = ascii_drop(b), punct = ascii_punct(b);
     const uint64_t chm = __ballot(!space && !drop && !punct), pum = __ballot(punct), spm = __ballot(space);
     uint64_t rem = chm | pum | spm;  // kept bytes not consumed yet
     while (rem && np < need) {
@@ -202,23 +363,21 @@ __global__ __launch_bounds__(64) void wordpiece_kernel(Params p, const uint8_t* 
         const uint64_t run = rem & below_q;
         if ((run >> lane) & 1) {
           const int at = wlen + __popcll(run & lanes_below(lane));
-          if (at < kWordCap) s_word[at] = (uint8_t)b;
+          if (at < CAP) s_word[at] = (uint8_t)b;
         }
         wlen = min(wlen + __popcll(run), 1 << 20);
+        wch = min(wch + __popcll(run), 1 << 20);
         rem &= ~below_q;
-        if (q < 64) {
-          np += flush_word(p, ws, wlen, np, need, out);
-          wlen = 0;
-        }
+        if (q < 64) flush();
       } else {
         if (wlen) {  // a word from the previous chunk ends at this chunk's first kept byte
-          np += flush_word(p, ws, wlen, np, need, out);
-          wlen = 0;
+          flush();
           continue;
         }
         if ((pum >> first) & 1) {
           if (lane == first) s_word[0] = (uint8_t)b;
-          np += flush_word(p, ws, 1, np, need, out);
+          wlen = wch = 1;
+          flush();
           rem &= rem - 1;
         } else {
           const uint64_t next = rem & ~spm;
@@ -227,8 +386,16 @@ __global__ __launch_bounds__(64) void wordpiece_kernel(Params p, const uint8_t* 
       }
     }
   }
-  if (wlen && np < need) np += flush_word(p, ws, wlen, np, need, out);
+  if (wlen && np < need && !bad) flush();
   np = min(np, need);
+  if (bad) {  // UTF8 only: nothing of the row stands
+    for (int j = lane; j < L; j += 64) {
+      out[j] = p.pad_id;
+      if (mask) mask[(size_t)row * L + j] = 0;
+    }
+    if (len && lane == 0) len[row] = -1;
+    return;
+  }
   if (lane == 0) {
     out[0] = p.cls_id;
     out[np + 1] = p.sep_id;
@@ -241,11 +408,48 @@ __global__ __launch_bounds__(64) void wordpiece_kernel(Params p, const uint8_t* 
 
 struct mec_tokenizer {
   int kind = 0, device = 0;
-  mec::DevBuf image;  // slots | pool | delim
+  mec::DevBuf image;  // slots | pool | delim, then (WORDPIECE_UTF8) cp index | cp blocks | cp outputs
   mec::tok::Params p{};
 };
 
 using namespace mec;
+
+namespace {
+
+size_t pad16(size_t n) { return (n + 15) / 16 * 16; }
+
+// Uploads the tables as one allocation and fills the handle. `cp` is null but for WORDPIECE_UTF8.
+int create(const mec_tok_desc* d, const tok::HostTable& t, const tok::CpTable* cp, int device, mec_tokenizer** out) {
+  MEC_HIP(hipSetDevice(device));
+  const size_t slot_bytes = t.slots.size() * sizeof(tok::Slot);
+  const size_t pool_bytes = pad16(t.pool.size());
+  const size_t index_at = slot_bytes + pool_bytes + 256;
+  const size_t block_at = index_at + (cp ? pad16(cp->index.size() * sizeof(uint16_t)) : 0);
+  const size_t exp_at = block_at + (cp ? pad16(cp->block.size() * sizeof(uint32_t)) : 0);
+  std::vector<uint8_t> image(exp_at + (cp ? pad16(cp->exp.size()) : 0), 0);
+  std::memcpy(image.data(), t.slots.data(), slot_bytes);
+  if (!t.pool.empty()) std::memcpy(image.data() + slot_bytes, t.pool.data(), t.pool.size());
+  std::memcpy(image.data() + slot_bytes + pool_bytes, d->delim, 256);
+  if (cp) {
+    std::memcpy(image.data() + index_at, cp->index.data(), cp->index.size() * sizeof(uint16_t));
+    std::memcpy(image.data() + block_at, cp->block.data(), cp->block.size() * sizeof(uint32_t));
+    if (!cp->exp.empty()) std::memcpy(image.data() + exp_at, cp->exp.data(), cp->exp.size());
+  }
+  auto* h = new mec_tokenizer;
+  h->kind = d->kind;
+  h->device = device;
+  if (upload(h->image, image.data(), image.size()) != 0) { delete h; return -1; }
+  uint8_t* base = h->image.as<uint8_t>();
+  h->p = tok::Params{reinterpret_cast<const tok::Slot*>(base), base + slot_bytes, base + slot_bytes + pool_bytes,
+                     (uint32_t)(t.slots.size() - 1), t.max_len, d->oov_id, d->lower, d->unk_id, d->cls_id,
+                     d->sep_id, d->pad_id, d->max_word,
+                     reinterpret_cast<const uint16_t*>(base + index_at),
+                     reinterpret_cast<const uint32_t*>(base + block_at), base + exp_at};
+  *out = h;
+  return 0;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -256,25 +460,24 @@ int mec_tok_create(const mec_tok_desc* d, int device, mec_tokenizer** out) {
     tok::HostTable t;
     std::string err;
     if (tok::build(d, &t, &err) != 0) { set_error(err); return -1; }
-    MEC_HIP(hipSetDevice(device));
-    const size_t slot_bytes = t.slots.size() * sizeof(tok::Slot);
-    const size_t pool_bytes = (t.pool.size() + 15) / 16 * 16;
-    std::vector<uint8_t> image(slot_bytes + pool_bytes + 256, 0);
-    std::memcpy(image.data(), t.slots.data(), slot_bytes);
-    if (!t.pool.empty()) std::memcpy(image.data() + slot_bytes, t.pool.data(), t.pool.size());
-    std::memcpy(image.data() + slot_bytes + pool_bytes, d->delim, 256);
-    auto* h = new mec_tokenizer;
-    h->kind = d->kind;
-    h->device = device;
-    if (upload(h->image, image.data(), image.size()) != 0) { delete h; return -1; }
-    uint8_t* base = h->image.as<uint8_t>();
-    h->p = tok::Params{reinterpret_cast<const tok::Slot*>(base), base + slot_bytes, base + slot_bytes + pool_bytes,
-                       (uint32_t)(t.slots.size() - 1), t.max_len, d->oov_id, d->lower, d->unk_id, d->cls_id,
-                       d->sep_id, d->pad_id, d->max_word};
-    *out = h;
-    return 0;
+    return create(d, t, nullptr, device, out);
   } catch (const std::exception& e) {
     set_error(std::string("mec_tok_create: ") + e.what());
+    return -1;
+  }
+}
+
+int mec_tok_create_utf8(const mec_tok_desc* d, const mec_tok_cpmap* m, int device, mec_tokenizer** out) {
+  try {
+    if (!out) { set_error("mec_tok_create_utf8: out is null"); return -1; }
+    *out = nullptr;
+    tok::HostTable t;
+    tok::CpTable cp;
+    std::string err;
+    if (tok::build(d, &t, &err, true) != 0 || tok::build_cpmap(m, d->lower, &cp, &err) != 0) { set_error(err); return -1; }
+    return create(d, t, &cp, device, out);
+  } catch (const std::exception& e) {
+    set_error(std::string("mec_tok_create_utf8: ") + e.what());
     return -1;
   }
 }
@@ -283,15 +486,17 @@ int mec_tok_encode(mec_tokenizer* t, const uint8_t* text, const int64_t* text_of
                    int32_t* mask, int32_t* len, void* stream) {
   MEC_REQUIRE(t, "mec_tok_encode: null tokenizer");
   MEC_REQUIRE(B >= 0, "mec_tok_encode: B < 0");
-  const int lmin = t->kind == MEC_TOK_WORDPIECE ? 2 : 1;
+  const int lmin = t->kind == MEC_TOK_KERAS ? 1 : 2;
   MEC_REQUIRE(L >= lmin && L <= 512, "mec_tok_encode: L must be in 1..512 (WORDPIECE: 2..512)");
   if (B == 0) return 0;
   MEC_REQUIRE(text && text_off && ids, "mec_tok_encode: text, text_off or ids is null");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (t->kind == MEC_TOK_KERAS)
     hipLaunchKernelGGL(tok::keras_kernel, dim3(B), dim3(64), 0, s, t->p, text, text_off, B, L, ids, mask, len);
+  else if (t->kind == MEC_TOK_WORDPIECE)
+    hipLaunchKernelGGL(tok::wordpiece_kernel<false>, dim3(B), dim3(64), 0, s, t->p, text, text_off, B, L, ids, mask, len);
   else
-    hipLaunchKernelGGL(tok::wordpiece_kernel, dim3(B), dim3(64), 0, s, t->p, text, text_off, B, L, ids, mask, len);
+    hipLaunchKernelGGL(tok::wordpiece_kernel<true>, dim3(B), dim3(64), 0, s, t->p, text, text_off, B, L, ids, mask, len);
   MEC_LAUNCH_CHECK();
   return 0;
 }

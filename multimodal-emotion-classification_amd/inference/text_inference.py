@@ -6,7 +6,9 @@ The 12-layer encoder, pooler and classifier run as hand-written HIP kernels (csr
 csrc/gemm_glds.hip). Tokenisation: a local BertTokenizer directory at Config.BERT_MODEL_PATH (never a
 hub download), exactly the reference's call at :78-85, on the host by default; with tokenize='gpu' the
 batched calls tokenize in the HIP kernel of csrc/tokenizer.hip (engine.GpuTokenizer: the same ids and
-mask; texts that are not 7-bit or hold a special-token literal keep the host tokenizer, row by row).
+mask; texts that are not 7-bit or hold a special-token literal keep the host tokenizer, row by row). With
+tokenize='gpu_utf8' non-ASCII texts are tokenized in the kernel too (a lower-casing, accent-stripping
+tokenizer only); the host keeps a text with a special-token literal or a code point outside the covered set.
 
 Added beyond the reference: predict_ids(ids, mask) for pre-tokenised input and
 predict_batch(ids, mask) for a device-resident [B,128] batch.
@@ -72,8 +74,8 @@ def encode_batch(tokenizer, texts):
 
 class TextInference:
     def __init__(self, weights=None, seed=None, device=None, tokenizer=None, precision=None, tokenize='host'):
-        if tokenize not in ('host', 'gpu'):
-            raise ValueError(f"tokenize must be 'host' or 'gpu', got {tokenize!r}")
+        if tokenize not in ('host', 'gpu', 'gpu_utf8'):
+            raise ValueError(f"tokenize must be 'host', 'gpu' or 'gpu_utf8', got {tokenize!r}")
         self.emotions = Config.EMOTIONS
         self.model = None
         self.preprocessor = _Cleaner()
@@ -85,13 +87,14 @@ class TextInference:
         self.device = self.model.device if self.model is not None else None
         self.tokenize = tokenize
         self.gpu_tokenizer = None
-        if tokenize == 'gpu':
+        if tokenize != 'host':
             if self.model is None or self.tokenizer is None:
-                raise ValueError("tokenize='gpu' needs the model and a tokenizer")
+                raise ValueError(f"tokenize='{tokenize}' needs the model and a tokenizer")
             # its host rows come from the tokenizer the batched host path uses (the fast one when there is one)
             self._host_fast()
             self.gpu_tokenizer = engine.GpuTokenizer.from_bert(self._fast or self.tokenizer, device=self.device,
-                                                               max_length=Config.MAX_TEXT_LENGTH)
+                                                               max_length=Config.MAX_TEXT_LENGTH,
+                                                               unicode=tokenize == 'gpu_utf8')
 
     def _keyword_heuristic(self, text: str) -> Dict:
         cleaned = self.preprocessor.clean_text(text)
@@ -152,7 +155,7 @@ class TextInference:
     def encode_batch(self, texts):
         """int32 ids / mask [B,128] for a list of strings (the fast tokenizer from the same
         vocab when available: same ids as the reference's BertTokenizer, tests/test_tokenizer.py).
-        tokenize='gpu': the same integers as device tensors (engine.GpuTokenizer.encode)."""
+        tokenize='gpu' / 'gpu_utf8': the same integers as device tensors (engine.GpuTokenizer.encode)."""
         if self.gpu_tokenizer is not None:
             return self.gpu_tokenizer.encode(texts)[:2]
         self._host_fast()
@@ -177,6 +180,8 @@ class TextInference:
         if self.gpu_tokenizer is not None:
             ids, mask, n = self.gpu_tokenizer.encode(texts)
             lens = n.cpu().numpy() if pack else None
+            if pack and (lens < 0).any():  # the routing predicate keeps such a text on the host
+                raise MecError('mec_tok_encode: a text the kernel does not cover reached it')
         else:
             ids, mask = self.encode_batch(texts)
             lens = mask.sum(1).astype(np.int32) if pack else None

@@ -76,6 +76,7 @@ SIGNATURES = {
     'mec_text_lstm_fwd': (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     'mec_lstm_seq_f32': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
     'mec_tok_create': (c_int, [c_vp, c_int, ctypes.POINTER(c_vp)]),
+    'mec_tok_create_utf8': (c_int, [c_vp, c_vp, c_int, ctypes.POINTER(c_vp)]),
     'mec_tok_encode': (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     'mec_tok_destroy': (c_int, [c_vp]),
     'mec_audio_fwd': (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp]),

@@ -349,19 +349,28 @@ class GpuTokenizer:
     truncation); both give exactly the host tokenizer's integers. A text the kernel's byte-level
     specification does not cover (mec.tokenize: WORDPIECE, a text that is not 7-bit or holds a special-token
     literal; either kind, a text without a UTF-8 encoding) is tokenized by `host_rows` and its row written
-    into the device result at its index, so the output order is the input order."""
+    into the device result at its index, so the output order is the input order. from_bert(unicode=True)
+    takes the WORDPIECE_UTF8 kind instead: any text stays on the GPU but one that holds a special-token
+    literal or a code point outside the covered set (mec.tokenize.wordpiece_cpmap)."""
 
-    def __init__(self, table: _tok.Table, host_rows, on_host=None, prepare=None, device=None, max_length: int = 128):
+    def __init__(self, table: _tok.Table, host_rows, on_host=None, prepare=None, device=None, max_length: int = 128,
+                 cpmap=None):
         self.lib = _lib.load()
         self.device = require_gpu(device)
-        self.table, self.L = table, int(max_length)
+        self.table, self.L, self.cpmap = table, int(max_length), cpmap
         self._host_rows, self._on_host, self._prepare = host_rows, on_host, prepare
         self.host_rows = 0  # rows the host tokenized in the last encode
         desc, keep = table.desc()
         h = ctypes.c_void_p()
         torch.cuda.set_device(self.device)
         self.handle = None
-        _lib.check(self.lib.mec_tok_create(ctypes.byref(desc), self.device.index, ctypes.byref(h)), 'mec_tok_create')
+        if cpmap is None:
+            _lib.check(self.lib.mec_tok_create(ctypes.byref(desc), self.device.index, ctypes.byref(h)), 'mec_tok_create')
+        else:
+            cp, keep_cp = cpmap.struct()
+            _lib.check(self.lib.mec_tok_create_utf8(ctypes.byref(desc), ctypes.byref(cp), self.device.index,
+                                                    ctypes.byref(h)), 'mec_tok_create_utf8')
+            del keep_cp
         del keep
         self.handle = h
 
@@ -379,14 +388,20 @@ class GpuTokenizer:
         return cls(_tok.keras_table(wi), host_rows, None, (str.lower if wi.lower else None), device, max_length)
 
     @classmethod
-    def from_bert(cls, tokenizer, device=None, max_length: int = 128):
+    def from_bert(cls, tokenizer, device=None, max_length: int = 128, unicode: bool = False):
         """tokenizer: a transformers BertTokenizer / BertTokenizerFast. ValueError when it has added tokens
-        beyond its special tokens or strip_accents contradicts do_lower_case."""
+        beyond its special tokens or strip_accents contradicts do_lower_case. unicode=True: non-ASCII text
+        is tokenized on the GPU too (MEC_TOK_WORDPIECE_UTF8); ValueError unless the tokenizer lower-cases and
+        strips accents."""
         def host_rows(texts):
             enc = tokenizer(list(texts), add_special_tokens=True, max_length=max_length, padding='max_length',
                             truncation=True, return_tensors='np')
             mask = enc['attention_mask'].astype(np.int32)
             return enc['input_ids'].astype(np.int32), mask, mask.sum(1).astype(np.int32)
+        if unicode:
+            cpmap = _tok.wordpiece_cpmap(tokenizer)
+            return cls(_tok.wordpiece_table_utf8(tokenizer), host_rows,
+                       _tok.wordpiece_on_host_utf8(tokenizer.all_special_tokens, cpmap), None, device, max_length, cpmap)
         return cls(_tok.wordpiece_table(tokenizer), host_rows, _tok.wordpiece_on_host(tokenizer.all_special_tokens),
                    None, device, max_length)
 

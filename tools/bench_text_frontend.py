@@ -10,6 +10,13 @@ with pack=True (TextInference.predict_texts) the two settings alternate, after a
 clock runs from the list of strings to the synchronized probabilities on the host; medians and min / max
 over the repeats are reported, with the device-event time of mec_tok_encode alone and the share of rows
 routed to the host. Prints one JSON line; --out also writes it to a file.
+
+    python3 tools/bench_text_frontend.py --utf8-shares 0,0.02,0.3,1 --out profiles/text_frontend_utf8.json
+
+measures, instead, BERT f16 pack=True with tokenize='host', 'gpu' and 'gpu_utf8' alternating, once per
+share of non-ASCII texts (curly quotes, dashes, an ellipsis, accented vowels, emoji, no-break spaces put
+into the same seeded texts), with the rows each GPU setting routes to the host and the device-event time
+of mec_tok_encode for both WordPiece kinds on the same texts.
 """
 import argparse
 import json
@@ -60,6 +67,81 @@ def make_texts(words, n_batches, B, rng, non_ascii):
     return batches
 
 
+ACCENTS = {'a': 'á', 'e': 'é', 'i': 'ï', 'o': 'ô', 'u': 'ü'}
+RICH_VOCAB = ['—', '“', '”', '’', '…', '😀', '##😀']
+
+
+def enrich(text, rng):
+    """The text with what real input has: an accented vowel, a dash, curly quotes, an ellipsis, an emoji, a
+    no-break space (one to three of these; always at least one non-ASCII character)."""
+    ws = text.split(' ')
+    for k in rng.choice(6, int(rng.integers(1, 4)), replace=False).tolist():
+        i = int(rng.integers(len(ws)))
+        if k == 0:
+            hit = [j for j, c in enumerate(ws[i]) if c in ACCENTS]
+            ws[i] = ws[i][:hit[0]] + ACCENTS[ws[i][hit[0]]] + ws[i][hit[0] + 1:] if hit else ws[i] + '’s'
+        elif k == 1:
+            ws[i] += ' —'
+        elif k == 2:
+            ws[i] = '“' + ws[i] + '”'
+        elif k == 3:
+            ws[-1] = ws[-1].rstrip('.!?') + '…'
+        elif k == 4:
+            ws[i] += ' 😀' if rng.random() < 0.5 else '😀'
+        else:
+            ws[i] += '\xa0' + ws[i]
+    return ' '.join(ws)
+
+
+def utf8_report(a, dev, words, vocab, res):
+    """BERT f16 pack=True, three tokenize settings alternating, per share of non-ASCII texts."""
+    from transformers import BertTokenizerFast
+    from inference.text_inference import TextInference
+    B = a.batch
+    with tempfile.TemporaryDirectory() as d:
+        with open(os.path.join(d, 'vocab.txt'), 'w', encoding='utf-8') as f:
+            f.write('\n'.join(vocab + RICH_VOCAB) + '\n')
+        fast = BertTokenizerFast.from_pretrained(d)
+    kinds = ('host', 'gpu', 'gpu_utf8')
+    bert = {k: TextInference(seed=1234, device=dev, tokenizer=fast, precision='f16', tokenize=k) for k in kinds}
+    fns = {k: (lambda texts, m=m: m.predict_texts(texts, pack=True)) for k, m in bert.items()}
+    res['wordpiece_vocab'] = len(vocab + RICH_VOCAB)
+    res['shares'] = {}
+    for share in a.utf8_shares:
+        rng = np.random.default_rng(0)
+        batches = make_texts(words, a.batches, B, rng, 0.0)
+        batches = [[enrich(t, rng) if rng.random() < share else t for t in b] for b in batches]
+        assert bert['host'].predict_texts(batches[0], pack=True) == bert['gpu_utf8'].predict_texts(batches[0], pack=True)
+        for k, fn in fns.items():
+            for texts in batches:
+                fn(texts)
+            clocked(fn, batches, a.warmup, dev)
+        ms = {k: [] for k in kinds}
+        for r in range(a.repeats):
+            for k, fn in fns.items():
+                ms[k] += clocked(fn, [batches[r % len(batches)]], 1, dev)
+        out = {'non_ascii_texts_share': float(np.mean([not t.isascii() for b in batches for t in b])),
+               'mean_text_bytes': float(np.mean([len(t.encode()) for b in batches for t in b]))}
+        for k in kinds:
+            out[k] = summary(ms[k], B)
+        for k in kinds[1:]:
+            gt = bert[k].gpu_tokenizer
+            routed = []
+            for texts in batches:
+                gt.encode(texts)
+                routed.append(gt.host_rows / B)
+            out[k]['rows_routed_to_host_share'] = float(np.mean(routed))
+            out[k]['over_host_speedup'] = statistics.median(ms['host']) / statistics.median(ms[k])
+            ev = [encode_event_ms(gt, batches[0], 50) for _ in range(a.event_repeats)]
+            out[k]['tok_encode_event_ms'] = {'median': statistics.median(ev), 'min_max': [min(ev), max(ev)]}
+            out[k]['tokenize_only'] = summary(clocked(gt.encode, batches, a.repeats, dev), B)
+        out['host']['tokenize_only'] = summary(clocked(
+            lambda texts: [engine.to_device(x, dev) for x in bert['host'].encode_batch(texts)], batches, a.repeats, dev), B)
+        out['gpu_utf8_over_gpu_speedup'] = statistics.median(ms['gpu']) / statistics.median(ms['gpu_utf8'])
+        res['shares'][str(share)] = out
+    return res
+
+
 def clocked(fn, batches, repeats, device):
     out = []
     for r in range(repeats):
@@ -108,6 +190,9 @@ def main():
     ap.add_argument('--batches', type=int, default=4, help='distinct text batches, cycled')
     ap.add_argument('--non-ascii', type=float, default=0.02, help='share of texts made non-ASCII')
     ap.add_argument('--vocab', type=int, default=30000)
+    ap.add_argument('--utf8-shares', type=lambda v: [float(x) for x in v.split(',')], default=None,
+                    help="comma-separated shares of non-ASCII texts: measure BERT with 'host', 'gpu' and 'gpu_utf8' at each")
+    ap.add_argument('--event-repeats', type=int, default=11, help='--utf8-shares: event timings of mec_tok_encode')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -127,6 +212,11 @@ def main():
     res = {'device': torch.cuda.get_device_name(0), 'batch': B, 'repeats': a.repeats, 'warmup': a.warmup,
            'words_per_text': [6, 40], 'wordpiece_vocab': len(vocab), 'non_ascii_share': a.non_ascii,
            'mean_text_bytes': float(np.mean([len(t.encode()) for b in batches for t in b]))}
+
+    if a.utf8_shares is not None:
+        del res['non_ascii_share'], res['mean_text_bytes']
+        finish(utf8_report(a, dev, words, vocab, res), a.out)
+        return
 
     wi = KerasWordIndex({'<OOV>': 1, **{w: i + 2 for i, w in enumerate(words)}}, num_words=10000)
     lstm = {k: FastTextEmotionPredictor(seed=1234, device=dev, word_index=wi, tokenize=k) for k in ('host', 'gpu')}
@@ -164,11 +254,14 @@ def main():
             gpu_tok = gt.encode
         res[name]['tokenize_only'] = {'host': summary(clocked(host_tok, batches, a.repeats, dev), B),
                                       'gpu': summary(clocked(gpu_tok, batches, a.repeats, dev), B)}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, 'w') as f:
+    finish(res, a.out)
+
+
+def finish(res, out):
+    print(json.dumps(res))
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, 'w') as f:
             f.write(json.dumps(res, indent=1) + '\n')
 
 
