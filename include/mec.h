@@ -257,6 +257,58 @@ int mec_fusion_fwd(mec_model* m, const float* s_feat, const float* t_feat, const
                    const float* s_pred, const float* t_pred, const float* i_pred, int B, float* logits,
                    float* probs, float* attn_w, float* dec_w, void* stream);
 
+/* Mixed-modality batches: B requests, each with any subset of {speech, text, image}, fused in one call
+ * that routes every row as MultimodalFusion.predict_multimodal routes one request
+ * (inference/multimodal_fusion.py:244-283). Each encoder runs once over the compact rows that have its
+ * modality; the fusion call reads them through index arrays (no gather or scatter copies).
+ *
+ * The plan is made on the host. present[b] is an or of the MEC_MOD_* bits of sample b. Compact order is
+ * ascending sample index: x_idx[b] (x = s, t, i) is the number of samples before b that have modality x,
+ * or -1 when sample b lacks it; counts = {ns, nt, ni}, the samples that have each modality. route[b] is
+ * MEC_ROUTE_NONE for no bit, MEC_ROUTE_SINGLE for one, MEC_ROUTE_AVERAGE for two and, when have_model == 0,
+ * for three, MEC_ROUTE_ATTENTION for three when have_model != 0. att holds the MEC_ROUTE_ATTENTION samples in
+ * ascending order, then -1 up to B. All arrays are on the HOST with B entries (counts 3). Returns n_att, the
+ * number of attention samples (0 for B == 0, which touches no array but counts, zeroed when given); -1 on
+ * error: B < 0, a null pointer with B > 0, a present value above 7. Uses no GPU. */
+enum { MEC_MOD_SPEECH = 1, MEC_MOD_TEXT = 2, MEC_MOD_IMAGE = 4 };
+enum { MEC_ROUTE_NONE = 0, MEC_ROUTE_SINGLE = 1, MEC_ROUTE_AVERAGE = 2, MEC_ROUTE_ATTENTION = 3 };
+int mec_fusion_mixed_plan(const uint8_t* present, int B, int have_model, int32_t* s_idx, int32_t* t_idx,
+                          int32_t* i_idx, int32_t* route, int32_t* att, int32_t counts[3]);
+
+/* The fusion step of a mixed batch. m: a MEC_FUSION handle, or NULL (no attention model: the plan was made
+ * with have_model == 0). Per sample b, with "present" meaning x_idx[b] >= 0:
+ *   attention  all three present and m != NULL (the samples att lists): the fusion model on
+ *              s_feat[s_idx[b]], t_feat[t_idx[b]], ... writes logits, attn_w, dec_w at row b and its float32
+ *              probs, widened to double (exact), at fused[b]. Bit-identical to mec_fusion_fwd on the same
+ *              rows gathered densely at the same "fusion_r" / "fusion_split": the kernels keep one
+ *              accumulator set per row, so a row's bits depend on neither its group-mates nor its slot.
+ *   average    two present, or three with m == NULL: fused[b] = fuse_predictions of the row in float64, a
+ *              missing modality as zeros (mec_fuse_weighted's arithmetic, one device function).
+ *   single     fused[b] = that modality's probs widened to double.
+ *   none       fused[b] = zeros.
+ * Every row off the attention route gets zeros in logits, attn_w and dec_w: the call writes every element
+ * of its four outputs, so callers need not clear them.
+ * The index arrays and att are on the DEVICE. The library trusts them (as mec_text_fwd_packed trusts its
+ * plan) but clamps every index into its array, x_idx to [-1, n_x - 1] and att entries to [0, B - 1]: a wrong
+ * plan gives wrong rows, never an access outside the arrays.
+ * B == 0 returns 0 without a launch. Returns -1 before any launch for: a null descriptor; with B > 0 a null
+ * index array or output; a negative count or one above B; n_att > 0 with m == NULL or with att NULL;
+ * n_att > min(ns, nt, ni); a handle of another kind; a compact array that is NULL while its count is > 0
+ * (the three feature arrays may be NULL when m == NULL). Asynchronous on `stream`, no synchronization; its
+ * only allocation is the handle's workspace. At most one launch beyond the attention model's own. */
+typedef struct mec_fusion_mixed_args {
+  const float *s_feat, *t_feat, *i_feat; /* compact f32 [ns,64] [nt,768] [ni,512] */
+  const float *s_pred, *t_pred, *i_pred; /* compact f32 [ns,7] [nt,7] [ni,7] */
+  int ns, nt, ni;
+  const int32_t *s_idx, *t_idx, *i_idx; /* device int32[B], a plan as above */
+  const int32_t* att;                   /* device int32[>= n_att] */
+  int n_att;
+  int B;
+  double* fused;                 /* [B,7] the row's answer */
+  float *logits, *attn_w, *dec_w; /* [B,7] [B,3] [B,3] */
+} mec_fusion_mixed_args;
+int mec_fusion_fwd_mixed(mec_model* m, const mec_fusion_mixed_args* a, void* stream);
+
 /* Speech features on the GPU (MEC_AUDIO handle; blob = {sample_rate, 2048, 512, 128, n_mfcc},
  * i.e. config.py's SAMPLE_RATE / N_MFCC and librosa's n_fft / hop / n_mels). wave: f32[B, n]
  * fixed-length waveforms (load_audio's pad/trim applied). feat: f32[B, n_mfcc + 16] =

@@ -251,6 +251,58 @@ int mec_fusion_fwd(mec_model* m, const float* s_feat, const float* t_feat, const
   })
 }
 
+}  // extern "C"
+
+// mec_fusion_mixed_plan's body (include/mec.h states it): one pass in ascending sample order. Host only.
+static int fusion_mixed_plan(const uint8_t* present, int B, int have_model, int32_t* s_idx, int32_t* t_idx,
+                             int32_t* i_idx, int32_t* route, int32_t* att, int32_t* counts) {
+  MEC_REQUIRE(B >= 0, "mec_fusion_mixed_plan: B < 0");
+  if (B == 0) {
+    if (counts) counts[0] = counts[1] = counts[2] = 0;
+    return 0;
+  }
+  MEC_REQUIRE(present && s_idx && t_idx && i_idx && route && att && counts,
+              "mec_fusion_mixed_plan: null pointer (present, the three index arrays, route and att hold B entries, counts 3)");
+  for (int b = 0; b < B; ++b)
+    MEC_REQUIRE(present[b] <= 7, "mec_fusion_mixed_plan: every present value must be an or of the MEC_MOD_* bits (0..7)");
+  int32_t* idx[3] = {s_idx, t_idx, i_idx};
+  int n[3] = {0, 0, 0}, n_att = 0;
+  for (int b = 0; b < B; ++b) {
+    int bits = 0;
+    for (int m = 0; m < 3; ++m) {
+      const bool has = (present[b] >> m) & 1;
+      idx[m][b] = has ? n[m]++ : -1;
+      bits += has;
+    }
+    route[b] = bits == 3 ? (have_model ? MEC_ROUTE_ATTENTION : MEC_ROUTE_AVERAGE) : bits;  // 0 none, 1 single, 2 average
+    if (route[b] == MEC_ROUTE_ATTENTION) att[n_att++] = b;
+  }
+  for (int k = n_att; k < B; ++k) att[k] = -1;
+  for (int m = 0; m < 3; ++m) counts[m] = n[m];
+  return n_att;
+}
+
+extern "C" {
+
+int mec_fusion_mixed_plan(const uint8_t* present, int B, int have_model, int32_t* s_idx, int32_t* t_idx, int32_t* i_idx,
+                          int32_t* route, int32_t* att, int32_t counts[3]) {
+  API_GUARD({ return fusion_mixed_plan(present, B, have_model, s_idx, t_idx, i_idx, route, att, counts); })
+}
+
+int mec_fusion_fwd_mixed(mec_model* m, const mec_fusion_mixed_args* a, void* stream) {
+  API_GUARD({
+    MEC_TRY(fusion_mixed_check(a, m != nullptr));
+    if (m && !m->impl) { set_error("null model handle"); return -1; }
+    if (m && m->impl->kind != KIND_FUSION) { set_error("model handle has the wrong kind for this call"); return -1; }
+    if (a->B == 0) return 0;
+    if (!m) return fusion_fwd_mixed(nullptr, *a, S(stream));
+    auto* p = as<FusionModel>(m, KIND_FUSION);
+    if (!p) return -1;
+    OptScope sc(&p->opts, &p->tune, p->range_dev);
+    return fusion_fwd_mixed(p, *a, S(stream));
+  })
+}
+
 int mec_audio_fwd(mec_model* m, const float* wave, int B, int n_samples, float* feat, float* tuning, void* stream) {
   API_GUARD({
     auto* p = as<AudioModel>(m, KIND_AUDIO);

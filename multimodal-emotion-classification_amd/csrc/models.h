@@ -2,6 +2,7 @@
 // weights and a grow-only activation workspace; forwards are asynchronous on the caller's
 // stream. One handle is used by one host thread at a time (the Python wrapper locks).
 #pragma once
+#include "../../include/mec.h"
 #include "mec_common.h"
 
 namespace mec {
@@ -75,6 +76,7 @@ struct AudioModel : Model {
 };
 
 // ---------------------------------------------------------------- fusion model
+struct FusionRows;  // speech_fusion.hip: which rows a fusion workgroup reads and writes
 struct FusionModel : Model {
   DevBuf w;  // fp32, transposed Linear weights ([in][out]) + biases + LN params
   std::vector<size_t> off;  // offsets by FusionParam index
@@ -83,7 +85,13 @@ struct FusionModel : Model {
   int forward(const float* sf, const float* tf, const float* imf, const float* sp, const float* tp,
               const float* ip, int B, float* logits, float* probs, float* attn_w, float* dec_w,
               hipStream_t s);
+  // the attention model's launches over B group rows (dense, or the rows x lists)
+  int launch(const float* sf, const float* tf, const float* imf, const float* sp, const float* tp, const float* ip,
+             int B, const FusionRows& x, float* logits, float* probs, float* attn_w, float* dec_w, hipStream_t s);
 };
+// mec_fusion_fwd_mixed: the argument checks (no handle, no device), then the call (p null: no model)
+int fusion_mixed_check(const mec_fusion_mixed_args* a, bool have_model);
+int fusion_fwd_mixed(FusionModel* p, const mec_fusion_mixed_args& a, hipStream_t s);
 
 int fuse_weighted(const float* s, const float* t, const float* i, int B, double* out, hipStream_t st);
 int fuse_weighted_f64(const double* s, const double* t, const double* i, int B, double* out, hipStream_t st);

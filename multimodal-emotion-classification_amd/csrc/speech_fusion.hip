@@ -8,6 +8,8 @@
 // fusion_kernel   restates MultiModalFusionModel.forward (inference/multimodal_fusion.py:
 //                 156-180) + the softmax of fuse_with_attention (:221).
 // fuse_weighted   restates fuse_predictions (:184-199) in float64 like numpy.
+// fusion_fwd_mixed  restates predict_multimodal's routing (:244-287) for a batch whose samples each have
+//                 any subset of the modalities: the fusion kernels over an index list, one row kernel for the rest.
 #include "block_ops.h"
 #include "models.h"
 
@@ -382,6 +384,38 @@ struct FusionW { const float* p[FUSION_NP]; };
 // 145 / 139 / 118 us at R = 1 / 2 / 4, the single kernel 174 us at R = 2.
 constexpr int F_LDIN = 1368, F_LDP = 768, F_LDT = 1280;
 
+// Which rows a fusion workgroup works on. Dense (att == nullptr, mec_fusion_fwd): group row g is sample g
+// of every array. Indexed (mec_fusion_fwd_mixed): group row g is sample att[g] of the [B] outputs and row
+// idx[m][att[g]] of modality m's compact [n[m], .] arrays; Pg / Tg stay compact by g. Every index is
+// clamped into its array (att to [0, B-1], idx to [-1, n-1]; -1 reads zeros), so a wrong plan gives
+// wrong rows, never an access outside them. fused != nullptr: the probs go there widened to double
+// instead of to `probs`.
+struct FusionRows {
+  const int32_t* att;
+  const int32_t* idx[3];
+  int B, n[3];
+  double* fused;
+};
+
+// rows[r] = {sample, speech row, text row, image row} of group row r0 + r, -1 past the last row (nr).
+// block_linear keeps one accumulator set per row, so the bits of a row depend on its values alone.
+template <int R>
+__device__ void fusion_stage_rows(const FusionRows& x, int r0, int nr, int (*rows)[4]) {
+  if (threadIdx.x < 4 * R) {
+    const int r = threadIdx.x >> 2, j = threadIdx.x & 3;
+    int v = -1;
+    if (r < nr) {
+      v = r0 + r;
+      if (x.att) {
+        v = min(max(x.att[v], 0), x.B - 1);
+        if (j) v = min(max(x.idx[j - 1][v], -1), x.n[j - 1] - 1);
+      }
+    }
+    rows[r][j] = v;
+  }
+  __syncthreads();
+}
+
 template <int FUSION_R>
 __device__ void cross_attention_rows(float* T, int ldt, int nr) {
   // T[r][0:256]=q, [256]=k0, [512]=k1, [768]=v0, [1024]=v1; writes o into T[r][0:256].
@@ -415,18 +449,22 @@ template <int FUSION_R>
 __global__ __launch_bounds__(512) void fusion_kernel(FusionW w, const float* __restrict__ sf,
                                                      const float* __restrict__ tf, const float* __restrict__ imf,
                                                      const float* __restrict__ sp, const float* __restrict__ tp,
-                                                     const float* __restrict__ ip, int B, float* logits,
-                                                     float* probs, float* attn_w, float* dec_w) {
+                                                     const float* __restrict__ ip, int B, FusionRows x,
+                                                     float* logits, float* probs, float* attn_w, float* dec_w) {
   constexpr int R = FUSION_R;
   __shared__ __attribute__((aligned(16))) float IN[R * F_LDIN], P[R * F_LDP], E[R * F_LDP], T[R * F_LDT], red[4 * R * SF_THREADS];
+  __shared__ int rows[R][4];
   const int tid = threadIdx.x, T_ = blockDim.x;
   const int r0 = blockIdx.x * R;
   const int nr = min(R, B - r0);
+  fusion_stage_rows<R>(x, r0, nr, rows);
   for (int idx = tid; idx < R * F_LDIN; idx += T_) {
     const int r = idx / F_LDIN, k = idx - r * F_LDIN;
-    const size_t b = (size_t)(r0 + r);
+    const int m = k < 64 ? 0 : (k < 832 ? 1 : (k < 1344 ? 2 : (k < 1351 ? 0 : (k < 1358 ? 1 : 2))));
+    const int row = rows[r][1 + m];
     float v = 0.f;
-    if (r < nr) {
+    if (row >= 0) {
+      const size_t b = (size_t)row;
       if (k < 64) v = sf[b * 64 + k];
       else if (k < 832) v = tf[b * 768 + (k - 64)];
       else if (k < 1344) v = imf[b * 512 + (k - 832)];
@@ -477,7 +515,7 @@ __global__ __launch_bounds__(512) void fusion_kernel(FusionW w, const float* __r
   }
   for (int idx = tid; idx < nr * 3; idx += T_) {
     const int r = idx / 3, j = idx - r * 3;
-    attn_w[(size_t)(r0 + r) * 3 + j] = P[r * F_LDP + j];
+    attn_w[(size_t)rows[r][0] * 3 + j] = P[r * F_LDP + j];
   }
   __syncthreads();
   // decision weights over the 21-d concat of softmax outputs (:138-143, :171-175)
@@ -492,7 +530,7 @@ __global__ __launch_bounds__(512) void fusion_kernel(FusionW w, const float* __r
   }
   for (int idx = tid; idx < nr * 3; idx += T_) {
     const int r = idx / 3, j = idx - r * 3;
-    dec_w[(size_t)(r0 + r) * 3 + j] = P[r * F_LDP + 384 + j];
+    dec_w[(size_t)rows[r][0] * 3 + j] = P[r * F_LDP + 384 + j];
   }
   __syncthreads();
   // classifier on [fused, weighted_preds] (:145-154, :177-178)
@@ -502,13 +540,15 @@ __global__ __launch_bounds__(512) void fusion_kernel(FusionW w, const float* __r
   block_linear<R>(T + 256, F_LDT, 128, w.p[68], 7, w.p[69], 7, T + 384, F_LDT, red, BACT_NONE);
   for (int idx = tid; idx < nr * 7; idx += T_) {
     const int r = idx / 7, c = idx - r * 7;
-    logits[(size_t)(r0 + r) * 7 + c] = T[r * F_LDT + 384 + c];
+    logits[(size_t)rows[r][0] * 7 + c] = T[r * F_LDT + 384 + c];
   }
   __syncthreads();
   block_softmax_small<R>(T + 384, F_LDT, 7, nullptr, 0);
   for (int idx = tid; idx < nr * 7; idx += T_) {
     const int r = idx / 7, c = idx - r * 7;
-    probs[(size_t)(r0 + r) * 7 + c] = T[r * F_LDT + 384 + c];
+    const float p = T[r * F_LDT + 384 + c];
+    if (x.fused) x.fused[(size_t)rows[r][0] * 7 + c] = (double)p;
+    else probs[(size_t)rows[r][0] * 7 + c] = p;
   }
 }
 
@@ -524,15 +564,18 @@ __global__ __launch_bounds__(512) void fusion_kernel(FusionW w, const float* __r
 template <int R>
 __global__ __launch_bounds__(512) void fusion_proj_kernel(FusionW w, const float* __restrict__ sf,
                                                           const float* __restrict__ tf, const float* __restrict__ imf,
-                                                          int B, float* __restrict__ Pg) {
+                                                          int B, FusionRows x, float* __restrict__ Pg) {
   __shared__ __attribute__((aligned(16))) float IN[R * 768], P[R * 256], red[4 * R * SF_THREADS];
+  __shared__ int rows[R][4];
   const int tid = threadIdx.x, m = blockIdx.y;
   const int r0 = blockIdx.x * R, nr = min(R, B - r0);
   const int dim = m == 0 ? 64 : (m == 1 ? 768 : 512);
   const float* src = m == 0 ? sf : (m == 1 ? tf : imf);
+  fusion_stage_rows<R>(x, r0, nr, rows);
   for (int idx = tid; idx < R * dim; idx += blockDim.x) {
     const int r = idx / dim, k = idx - r * dim;
-    IN[r * 768 + k] = r < nr ? src[(size_t)(r0 + r) * dim + k] : 0.f;
+    const int row = rows[r][1 + m];
+    IN[r * 768 + k] = row >= 0 ? src[(size_t)row * dim + k] : 0.f;
   }
   __syncthreads();
   block_linear<R>(IN, 768, dim, w.p[4 * m], 256, w.p[4 * m + 1], 256, P, 256, red, BACT_NONE);
@@ -580,22 +623,25 @@ __global__ __launch_bounds__(512) void fusion_cross_kernel(FusionW w, const floa
 template <int R>
 __global__ __launch_bounds__(512) void fusion_head_kernel(FusionW w, const float* __restrict__ Tg,
                                                           const float* __restrict__ sp, const float* __restrict__ tp,
-                                                          const float* __restrict__ ip, int B, float* logits,
-                                                          float* probs, float* attn_w, float* dec_w) {
+                                                          const float* __restrict__ ip, int B, FusionRows x,
+                                                          float* logits, float* probs, float* attn_w, float* dec_w) {
   constexpr int LDPR = 24;
   __shared__ __attribute__((aligned(16))) float PR[R * LDPR], P[R * F_LDP], E[R * F_LDP], T[R * F_LDT], red[4 * R * SF_THREADS];
+  __shared__ int rows[R][4];
   const int tid = threadIdx.x, T_ = blockDim.x;
   const int r0 = blockIdx.x * R;
   const int nr = min(R, B - r0);
+  fusion_stage_rows<R>(x, r0, nr, rows);
   for (int idx = tid; idx < R * 768; idx += T_) {
     const int r = idx / 768, k = idx - r * 768;
     T[r * F_LDT + k] = r < nr ? Tg[(size_t)(r0 + r) * 768 + k] : 0.f;
   }
   for (int idx = tid; idx < R * LDPR; idx += T_) {
     const int r = idx / LDPR, k = idx - r * LDPR;
-    const size_t b = (size_t)(r0 + r);
+    const int row = rows[r][1 + min(k / 7, 2)];
+    const size_t b = (size_t)row;
     float v = 0.f;
-    if (r < nr) {
+    if (row >= 0) {
       if (k < 7) v = sp[b * 7 + k];
       else if (k < 14) v = tp[b * 7 + (k - 7)];
       else if (k < 21) v = ip[b * 7 + (k - 14)];
@@ -614,7 +660,7 @@ __global__ __launch_bounds__(512) void fusion_head_kernel(FusionW w, const float
   }
   for (int idx = tid; idx < nr * 3; idx += T_) {
     const int r = idx / 3, j = idx - r * 3;
-    attn_w[(size_t)(r0 + r) * 3 + j] = P[r * F_LDP + j];
+    attn_w[(size_t)rows[r][0] * 3 + j] = P[r * F_LDP + j];
   }
   __syncthreads();
   block_linear<R>(PR, LDPR, 21, w.p[58], 64, w.p[59], 64, P + 256, F_LDP, red, BACT_RELU);
@@ -628,7 +674,7 @@ __global__ __launch_bounds__(512) void fusion_head_kernel(FusionW w, const float
   }
   for (int idx = tid; idx < nr * 3; idx += T_) {
     const int r = idx / 3, j = idx - r * 3;
-    dec_w[(size_t)(r0 + r) * 3 + j] = P[r * F_LDP + 384 + j];
+    dec_w[(size_t)rows[r][0] * 3 + j] = P[r * F_LDP + 384 + j];
   }
   __syncthreads();
   block_linear<R>(E, F_LDP, 263, w.p[62], 256, w.p[63], 256, T, F_LDT, red, BACT_NONE);
@@ -637,25 +683,32 @@ __global__ __launch_bounds__(512) void fusion_head_kernel(FusionW w, const float
   block_linear<R>(T + 256, F_LDT, 128, w.p[68], 7, w.p[69], 7, T + 384, F_LDT, red, BACT_NONE);
   for (int idx = tid; idx < nr * 7; idx += T_) {
     const int r = idx / 7, c = idx - r * 7;
-    logits[(size_t)(r0 + r) * 7 + c] = T[r * F_LDT + 384 + c];
+    logits[(size_t)rows[r][0] * 7 + c] = T[r * F_LDT + 384 + c];
   }
   __syncthreads();
   block_softmax_small<R>(T + 384, F_LDT, 7, nullptr, 0);
   for (int idx = tid; idx < nr * 7; idx += T_) {
     const int r = idx / 7, c = idx - r * 7;
-    probs[(size_t)(r0 + r) * 7 + c] = T[r * F_LDT + 384 + c];
+    const float p = T[r * F_LDT + 384 + c];
+    if (x.fused) x.fused[(size_t)rows[r][0] * 7 + c] = (double)p;
+    else probs[(size_t)rows[r][0] * 7 + c] = p;
   }
 }
 
 template <int R>
-static void launch_fusion_split(const FusionW& p, const float* sf, const float* tf, const float* imf, const float* sp,
-                                const float* tp, const float* ip, int B, float* Pg, float* Tg, float* logits,
-                                float* probs, float* attn_w, float* dec_w, hipStream_t s) {
+static void launch_fusion(const FusionW& p, const float* sf, const float* tf, const float* imf, const float* sp,
+                          const float* tp, const float* ip, int B, const FusionRows& x, bool split, float* Pg,
+                          float* Tg, float* logits, float* probs, float* attn_w, float* dec_w, hipStream_t s) {
   const int groups = (B + R - 1) / R;
-  hipLaunchKernelGGL((fusion_proj_kernel<R>), dim3(groups, 3), dim3(SF_THREADS), 0, s, p, sf, tf, imf, B, Pg);
+  if (!split) {
+    hipLaunchKernelGGL((fusion_kernel<R>), dim3(groups), dim3(SF_THREADS), 0, s, p, sf, tf, imf, sp, tp, ip, B, x,
+                       logits, probs, attn_w, dec_w);
+    return;
+  }
+  hipLaunchKernelGGL((fusion_proj_kernel<R>), dim3(groups, 3), dim3(SF_THREADS), 0, s, p, sf, tf, imf, B, x, Pg);
   hipLaunchKernelGGL((fusion_cross_kernel<R>), dim3(groups, 3), dim3(SF_THREADS), 0, s, p, Pg, B, Tg);
-  hipLaunchKernelGGL((fusion_head_kernel<R>), dim3(groups), dim3(SF_THREADS), 0, s, p, Tg, sp, tp, ip, B, logits, probs,
-                     attn_w, dec_w);
+  hipLaunchKernelGGL((fusion_head_kernel<R>), dim3(groups), dim3(SF_THREADS), 0, s, p, Tg, sp, tp, ip, B, x, logits,
+                     probs, attn_w, dec_w);
 }
 
 int FusionModel::create(const float* blob, size_t n) {
@@ -708,6 +761,30 @@ int FusionModel::create(const float* blob, size_t n) {
   return upload(w, h.data(), h.size() * sizeof(float));
 }
 
+// The model's launches over B group rows (dense: the B samples; indexed: the n_att rows of x.att).
+int FusionModel::launch(const float* sf, const float* tf, const float* imf, const float* sp, const float* tp,
+                        const float* ip, int B, const FusionRows& x, float* logits, float* probs, float* attn_w,
+                        float* dec_w, hipStream_t s) {
+  FusionW p;
+  const float* base = w.as<float>();
+  for (int i = 0; i < FUSION_NP; ++i) p.p[i] = base + off[i];
+  const int R = opt().fusion_r;
+  const bool split = opt().fusion_split != 0;
+  float *Pg = nullptr, *Tg = nullptr;
+  if (split)
+    MEC_TRY(carve(ws, [&](Carver& c) {
+      Pg = c.take<float>((size_t)B * 768);
+      Tg = c.take<float>((size_t)B * 768);
+    }));
+  switch (R) {
+    case 1: launch_fusion<1>(p, sf, tf, imf, sp, tp, ip, B, x, split, Pg, Tg, logits, probs, attn_w, dec_w, s); break;
+    case 4: launch_fusion<4>(p, sf, tf, imf, sp, tp, ip, B, x, split, Pg, Tg, logits, probs, attn_w, dec_w, s); break;
+    default: launch_fusion<2>(p, sf, tf, imf, sp, tp, ip, B, x, split, Pg, Tg, logits, probs, attn_w, dec_w, s); break;
+  }
+  MEC_LAUNCH_CHECK();
+  return 0;
+}
+
 int FusionModel::forward(const float* sf, const float* tf, const float* imf, const float* sp,
                          const float* tp, const float* ip, int B, float* logits, float* probs,
                          float* attn_w, float* dec_w, hipStream_t s) {
@@ -715,52 +792,34 @@ int FusionModel::forward(const float* sf, const float* tf, const float* imf, con
   if (B == 0) return 0;
   MEC_REQUIRE(sf && tf && imf && sp && tp && ip && logits && probs && attn_w && dec_w,
               "fusion: null pointer (the attention model needs all three modalities)");
-  FusionW p;
-  const float* base = w.as<float>();
-  for (int i = 0; i < FUSION_NP; ++i) p.p[i] = base + off[i];
   MEC_TRY(prof.begin(TAG_FUSION, s));
-  const int R = opt().fusion_r;
-  const dim3 grid((B + R - 1) / R), blk(SF_THREADS);
-  if (opt().fusion_split) {
-    float *Pg, *Tg;
-    MEC_TRY(carve(ws, [&](Carver& c) {
-      Pg = c.take<float>((size_t)B * 768);
-      Tg = c.take<float>((size_t)B * 768);
-    }));
-    switch (R) {
-      case 1: launch_fusion_split<1>(p, sf, tf, imf, sp, tp, ip, B, Pg, Tg, logits, probs, attn_w, dec_w, s); break;
-      case 4: launch_fusion_split<4>(p, sf, tf, imf, sp, tp, ip, B, Pg, Tg, logits, probs, attn_w, dec_w, s); break;
-      default: launch_fusion_split<2>(p, sf, tf, imf, sp, tp, ip, B, Pg, Tg, logits, probs, attn_w, dec_w, s); break;
-    }
-    MEC_LAUNCH_CHECK();
-    MEC_TRY(prof.end(TAG_FUSION, s));
-    return 0;
-  }
-  switch (R) {
-    case 1: hipLaunchKernelGGL((fusion_kernel<1>), grid, blk, 0, s, p, sf, tf, imf, sp, tp, ip, B, logits, probs, attn_w, dec_w); break;
-    case 4: hipLaunchKernelGGL((fusion_kernel<4>), grid, blk, 0, s, p, sf, tf, imf, sp, tp, ip, B, logits, probs, attn_w, dec_w); break;
-    default: hipLaunchKernelGGL((fusion_kernel<2>), grid, blk, 0, s, p, sf, tf, imf, sp, tp, ip, B, logits, probs, attn_w, dec_w); break;
-  }
-  MEC_LAUNCH_CHECK();
+  MEC_TRY(launch(sf, tf, imf, sp, tp, ip, B, FusionRows{}, logits, probs, attn_w, dec_w, s));
   MEC_TRY(prof.end(TAG_FUSION, s));
   return 0;
 }
 
 // =============================================================== weighted average
+// fuse_predictions on one row, in float64 like numpy; a null row is a missing modality (zeros). The one
+// statement of this arithmetic: fuse_weighted_kernel and fusion_rows_kernel both call it.
 template <class T>
-__global__ void fuse_weighted_kernel(const T* s, const T* t, const T* i, int B, double* out) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
+__device__ void fuse_weighted_row(const T* s, const T* t, const T* i, double* out) {
   double w[7];
   for (int c = 0; c < 7; ++c) {
-    const double vs = s ? (double)s[b * 7 + c] : 0.0;
-    const double vt = t ? (double)t[b * 7 + c] : 0.0;
-    const double vi = i ? (double)i[b * 7 + c] : 0.0;
+    const double vs = s ? (double)s[c] : 0.0;
+    const double vt = t ? (double)t[c] : 0.0;
+    const double vi = i ? (double)i[c] : 0.0;
     w[c] = 0.3 * vs + 0.35 * vt + 0.35 * vi;  // weights [0.3, 0.35, 0.35] (multimodal_fusion.py:23)
   }
   double sum = 0.0;
   for (int c = 0; c < 7; ++c) sum += w[c];
-  for (int c = 0; c < 7; ++c) out[b * 7 + c] = sum > 0.0 ? w[c] / sum : w[c];
+  for (int c = 0; c < 7; ++c) out[c] = sum > 0.0 ? w[c] / sum : w[c];
+}
+
+template <class T>
+__global__ void fuse_weighted_kernel(const T* s, const T* t, const T* i, int B, double* out) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  fuse_weighted_row(s ? s + b * 7 : nullptr, t ? t + b * 7 : nullptr, i ? i + b * 7 : nullptr, out + b * 7);
 }
 
 template <class T>
@@ -778,6 +837,75 @@ int fuse_weighted(const float* s, const float* t, const float* i, int B, double*
 
 int fuse_weighted_f64(const double* s, const double* t, const double* i, int B, double* out, hipStream_t st) {
   return fuse_weighted_t<double>(s, t, i, B, out, st);
+}
+
+// =============================================================== mixed-modality batches
+// mec_fusion_fwd_mixed (include/mec.h): every sample routed as predict_multimodal routes one request
+// (multimodal_fusion.py:244-283). The attention rows run the fusion kernels above over the att list; one
+// thread per sample does the rest: the float64 average (two modalities, or three without a model), a single
+// modality's probs widened, zeros for none, and zeros in logits / attn_w / dec_w off the attention route.
+__global__ void fusion_rows_kernel(FusionRows x, int have_model, const float* __restrict__ sp,
+                                   const float* __restrict__ tp, const float* __restrict__ ip, float* logits,
+                                   float* attn_w, float* dec_w) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= x.B) return;
+  const float* pred[3] = {sp, tp, ip};
+  const float* row[3];
+  const float* one = nullptr;
+  int np = 0;
+  for (int m = 0; m < 3; ++m) {
+    const int r = min(max(x.idx[m][b], -1), x.n[m] - 1);
+    row[m] = r >= 0 ? pred[m] + (size_t)r * 7 : nullptr;
+    if (row[m]) { one = row[m]; ++np; }
+  }
+  if (np == 3 && have_model) return;  // the attention route: the fusion kernels write this sample
+  for (int c = 0; c < 7; ++c) logits[(size_t)b * 7 + c] = 0.f;
+  for (int j = 0; j < 3; ++j) attn_w[(size_t)b * 3 + j] = dec_w[(size_t)b * 3 + j] = 0.f;
+  double* out = x.fused + (size_t)b * 7;
+  if (np >= 2) {
+    fuse_weighted_row(row[0], row[1], row[2], out);
+  } else {
+    for (int c = 0; c < 7; ++c) out[c] = one ? (double)one[c] : 0.0;
+  }
+}
+
+// Everything mec_fusion_fwd_mixed can refuse without the handle or the device.
+int fusion_mixed_check(const mec_fusion_mixed_args* a, bool have_model) {
+  MEC_REQUIRE(a, "mec_fusion_fwd_mixed: null descriptor");
+  MEC_REQUIRE(a->B >= 0 && a->ns >= 0 && a->nt >= 0 && a->ni >= 0 && a->n_att >= 0,
+              "mec_fusion_fwd_mixed: negative count (B, ns, nt, ni, n_att)");
+  if (a->B == 0) return 0;
+  MEC_REQUIRE(a->s_idx && a->t_idx && a->i_idx, "mec_fusion_fwd_mixed: null index array (s_idx, t_idx, i_idx hold B entries)");
+  MEC_REQUIRE(a->fused && a->logits && a->attn_w && a->dec_w,
+              "mec_fusion_fwd_mixed: null output (fused, logits, attn_w, dec_w)");
+  MEC_REQUIRE(a->ns <= a->B && a->nt <= a->B && a->ni <= a->B && a->n_att <= a->B,
+              "mec_fusion_fwd_mixed: a count above B");
+  MEC_REQUIRE(a->n_att == 0 || have_model, "mec_fusion_fwd_mixed: n_att > 0 needs the fusion model (null handle)");
+  MEC_REQUIRE(a->n_att <= std::min(a->ns, std::min(a->nt, a->ni)),
+              "mec_fusion_fwd_mixed: n_att above min(ns, nt, ni) (an attention row has all three modalities)");
+  MEC_REQUIRE(a->n_att == 0 || a->att, "mec_fusion_fwd_mixed: null att with n_att > 0");
+  MEC_REQUIRE((a->ns == 0 || a->s_pred) && (a->nt == 0 || a->t_pred) && (a->ni == 0 || a->i_pred),
+              "mec_fusion_fwd_mixed: null probs of a modality whose count is > 0");
+  MEC_REQUIRE(!have_model || ((a->ns == 0 || a->s_feat) && (a->nt == 0 || a->t_feat) && (a->ni == 0 || a->i_feat)),
+              "mec_fusion_fwd_mixed: null features of a modality whose count is > 0");
+  return 0;
+}
+
+// p == nullptr: the row kernel alone (every multi-modality sample averaged). `a` has passed fusion_mixed_check.
+int fusion_fwd_mixed(FusionModel* p, const mec_fusion_mixed_args& a, hipStream_t s) {
+  if (a.B == 0) return 0;
+  FusionRows x{a.att, {a.s_idx, a.t_idx, a.i_idx}, a.B, {a.ns, a.nt, a.ni}, a.fused};
+  if (p) MEC_TRY(p->prof.begin(TAG_FUSION, s));
+  if (a.n_att < a.B) {  // a batch of attention samples alone leaves the row kernel nothing to write
+    hipLaunchKernelGGL(fusion_rows_kernel, dim3((a.B + 255) / 256), dim3(256), 0, s, x, p ? 1 : 0, a.s_pred, a.t_pred,
+                       a.i_pred, a.logits, a.attn_w, a.dec_w);
+    MEC_LAUNCH_CHECK();
+  }
+  if (p && a.n_att > 0)
+    MEC_TRY(p->launch(a.s_feat, a.t_feat, a.i_feat, a.s_pred, a.t_pred, a.i_pred, a.n_att, x, a.logits, nullptr,
+                      a.attn_w, a.dec_w, s));
+  if (p) MEC_TRY(p->prof.end(TAG_FUSION, s));
+  return 0;
 }
 
 }  // namespace mec

@@ -9,7 +9,9 @@ predict_multimodal follows the reference's control flow (:244-287) but runs each
 once: features and probabilities come out of the same forward.
 
 Added beyond the reference: predict_batch(x, ids, mask, gray) -> the whole batched path
-(mec.engine.FusedPipeline semantics) on device tensors.
+(mec.engine.FusedPipeline semantics) on device tensors, and predict_multimodal_batch(requests) ->
+predict_multimodal's result dicts for a batch of requests that each carry any subset of the modalities
+(one launch set per encoder over the rows that have it, one routed fusion call: mec_fusion_fwd_mixed).
 """
 
 from typing import Dict, Optional
@@ -19,11 +21,13 @@ import torch
 
 from config import Config
 from mec import checkpoints, engine
+from mec import _lib
 from mec._lib import MecError
 
+from inference import speech_inference as _speech
 from inference.speech_inference import SpeechInference
 from inference.text_inference import TextInference
-from inference.image_inference import ImageInference
+from inference.image_inference import ImageInference, _to_model_input
 
 _MODS = ('speech', 'text', 'image')
 
@@ -131,6 +135,116 @@ class MultimodalFusion:
         imf, il, ip = self.image_inference.predict_batch(gray)
         fl, fp, aw, dw = self.fusion_model.forward(sf, tf, imf, sp, tp, ip)
         return {'speech': (sf, sl, sp), 'text': (tf, tl, tp), 'image': (imf, il, ip), 'fusion': (fl, fp, aw, dw)}
+
+    def predict_multimodal_batch(self, requests):
+        """`predict_multimodal` for a batch: requests is a sequence of (audio_path, text, image_path)
+        tuples or dicts with those keys, a falsy entry meaning absent (the reference's `if audio_path:`).
+        -> one dict per request with the keys and value types predict_multimodal gives that request:
+        'speech' / 'text' / 'image' where present, 'fusion' for two or more modalities (with
+        'attention_weights' / 'decision_weights' on the attention route only), {} for an empty request.
+
+        Each encoder runs once over the requests that have its modality and one fusion call routes every
+        request (engine.FusionHead.forward_mixed; engine.fuse_mixed without a fusion model, where every
+        multi-modality request takes the average); one device-to-host copy at the end. Needs the three
+        encoder models (RuntimeError otherwise, as predict_batch). Files are read before any GPU work: one
+        that cannot be read raises ValueError naming its request (the heuristic and neutral fallbacks stay
+        with the per-request method)."""
+        for m, obj in (('speech', self.speech_inference), ('text', self.text_inference),
+                       ('image', self.image_inference)):
+            if obj.model is None:
+                raise RuntimeError(f'{m} model not loaded')
+        if self.text_inference.tokenizer is None:
+            raise RuntimeError('text tokenizer not loaded')
+        reqs = []
+        for r in requests:
+            a, t, i = (r.get('audio_path'), r.get('text'), r.get('image_path')) if isinstance(r, dict) else r
+            reqs.append((a or None, t or None, i or None))
+        present = np.array([[x is not None for x in r] for r in reqs], bool).reshape(-1, 3)
+        # ---- host: decode every file first
+        ap = _speech._preprocessing() if present[:, 0].any() else None
+        waves, wave_at, hostf, hostf_at = [], [], [], []  # compact speech rows: GPU features / host features
+        images = {}  # input shape -> (arrays, compact image rows)
+        ns = ni = 0
+        for b, (a, _, i) in enumerate(reqs):
+            if a is not None:
+                try:
+                    audio, sr = ap.load_audio(a)
+                    if int(sr) != Config.SAMPLE_RATE:  # as SpeechInference._file_features
+                        hostf.append(np.asarray(ap.preprocess_audio(a), np.float32).reshape(56))
+                        hostf_at.append(ns)
+                    else:
+                        waves.append(np.asarray(audio, np.float32).reshape(-1))
+                        wave_at.append(ns)
+                except Exception as e:
+                    raise ValueError(f'request {b}: cannot read audio {a!r}: {e}') from e
+                ns += 1
+            if i is not None:
+                try:
+                    from PIL import Image
+                    with Image.open(i) as im:
+                        arr = _to_model_input(im)
+                except Exception as e:
+                    raise ValueError(f'request {b}: cannot read image {i!r}: {e}') from e
+                arrs, at = images.setdefault(arr.shape, ([], []))
+                arrs.append(arr)
+                at.append(ni)
+                ni += 1
+        texts = [t for _, t, _ in reqs if t is not None]
+        dev = self.device
+        at_dev = lambda at: torch.tensor(at, dtype=torch.int64, device=dev)  # noqa: E731
+        # ---- encoders, each over its compact rows
+        speech = text = image = None
+        if ns:
+            x = torch.empty((ns, 56), dtype=torch.float32, device=dev)
+            if waves:
+                x.index_copy_(0, at_dev(wave_at),
+                              self.speech_inference.features_from_waveforms(engine.to_device(np.stack(waves), dev)))
+            if hostf:
+                x.index_copy_(0, at_dev(hostf_at), engine.to_device(np.stack(hostf), dev))
+            sf, _, sp = self.speech_inference.model.forward(x)
+            speech = (sf, sp)
+        if texts:
+            ids, mask = self.text_inference.encode_batch(texts)
+            if not isinstance(ids, torch.Tensor):
+                ids, mask = engine.to_device(ids, dev), engine.to_device(mask, dev)
+            tf, _, tp = self.text_inference.model.checked('forward', ids, mask)
+            text = (tf, tp)
+        if ni:
+            imf = torch.empty((ni, 512), dtype=torch.float32, device=dev)
+            ip = torch.empty((ni, 7), dtype=torch.float32, device=dev)
+            for arrs, at in images.values():  # one forward per input shape, placed in compact order
+                f, _, p = self.image_inference.model.checked('forward_u8', engine.to_device(np.stack(arrs), dev))
+                imf.index_copy_(0, at_dev(at), f)
+                ip.index_copy_(0, at_dev(at), p)
+            image = (imf, ip)
+        # ---- one routed fusion call
+        plan = engine.fusion_mixed_plan(present, self.fusion_model is not None, dev)
+        if self.fusion_model is not None:
+            fused, _, aw, dw = self.fusion_model.forward_mixed(plan, speech, text, image)
+        else:
+            fused, _, aw, dw = engine.fuse_mixed(plan, *(None if p is None else p[1] for p in (speech, text, image)))
+        # ---- the one device-to-host copy (float32 -> float64 is exact)
+        parts = [fused, aw, dw] + [p[1] for p in (speech, text, image) if p is not None]
+        host = torch.cat([p.reshape(-1).double() for p in parts]).cpu().numpy()
+        self.speech_inference.model.check()
+        cut = np.cumsum([0] + [p.numel() for p in parts])
+        views = [host[cut[k]:cut[k + 1]].reshape(parts[k].shape) for k in range(len(parts))]
+        fused, aw, dw = views[:3]
+        probs = dict(zip([m for m, p in zip(_MODS, (speech, text, image)) if p is not None], views[3:]))
+        as_dict = SpeechInference._as_dict
+        results = []
+        for b in range(len(reqs)):
+            res = {}
+            for m, idx in zip(_MODS, (plan.s_idx, plan.t_idx, plan.i_idx)):
+                if idx[b] >= 0:
+                    res[m] = as_dict(self.emotions, probs[m][idx[b]])
+            if plan.route[b] >= _lib.ROUTE_AVERAGE:
+                res['fusion'] = as_dict(self.emotions, fused[b])
+            if plan.route[b] == _lib.ROUTE_ATTENTION:
+                res['fusion']['attention_weights'] = {m: float(aw[b, j]) for j, m in enumerate(_MODS)}
+                res['fusion']['decision_weights'] = {m: float(dw[b, j]) for j, m in enumerate(_MODS)}
+            results.append(res)
+        return results
 
     def check(self):
         """After predict_batch: synchronize the device and raise MecError if a kernel flagged an

@@ -54,6 +54,19 @@ class AttnArgs(ctypes.Structure):
 
 X3_PAIRED = -1
 
+
+class FusionMixedArgs(ctypes.Structure):
+    """include/mec.h mec_fusion_mixed_args (mec_fusion_fwd_mixed's descriptor), field for field."""
+    _fields_ = [('s_feat', c_vp), ('t_feat', c_vp), ('i_feat', c_vp), ('s_pred', c_vp), ('t_pred', c_vp),
+                ('i_pred', c_vp), ('ns', c_int), ('nt', c_int), ('ni', c_int),
+                ('s_idx', c_vp), ('t_idx', c_vp), ('i_idx', c_vp), ('att', c_vp), ('n_att', c_int), ('B', c_int),
+                ('fused', c_vp), ('logits', c_vp), ('attn_w', c_vp), ('dec_w', c_vp)]
+
+
+# include/mec.h MEC_MOD_* (bits of a sample's `present`) and MEC_ROUTE_*
+MOD_SPEECH, MOD_TEXT, MOD_IMAGE = 1, 2, 4
+ROUTE_NONE, ROUTE_SINGLE, ROUTE_AVERAGE, ROUTE_ATTENTION = 0, 1, 2, 3
+
 # name -> (restype, argtypes); mirrors include/mec.h one to one.
 SIGNATURES = {
     'mec_version': (ctypes.c_char_p, []),
@@ -73,6 +86,8 @@ SIGNATURES = {
     'mec_image_fwd': (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
     'mec_image_fwd_u8': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     'mec_fusion_fwd': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'mec_fusion_mixed_plan': (c_int, [ctypes.POINTER(ctypes.c_uint8), c_int, c_int] + [ctypes.POINTER(ctypes.c_int32)] * 6),
+    'mec_fusion_fwd_mixed': (c_int, [c_vp, ctypes.POINTER(FusionMixedArgs), c_vp]),
     'mec_text_lstm_fwd': (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     'mec_lstm_seq_f32': (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
     'mec_tok_create': (c_int, [c_vp, c_int, ctypes.POINTER(c_vp)]),

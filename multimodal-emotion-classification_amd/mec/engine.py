@@ -533,6 +533,103 @@ class FusionHead(HipModel):
                                                _ptr(dw), _stream(self.device)), 'mec_fusion_fwd')
         return logits, probs, aw, dw
 
+    def forward_mixed(self, plan, speech, text, image):
+        """The fusion step of a mixed-modality batch (mec_fusion_fwd_mixed). plan: a `fusion_mixed_plan`
+        made with have_model=True; speech / text / image: a `(feat, probs)` pair of compact tensors
+        ([ns,64] / [nt,768] / [ni,512] and [n,7], the rows that have the modality in sample order), or None
+        when the plan's count is 0. -> (fused f64 [B,7], logits [B,7], attn_w [B,3], dec_w [B,3]): every
+        sample routed as predict_multimodal routes a request; zeros in the last three off the attention
+        route."""
+        if not plan.have_model:
+            raise ValueError('forward_mixed: the plan was made with have_model=False (engine.fuse_mixed takes it)')
+        with self._lock:
+            return _fusion_mixed(self.lib, self.handle, plan, (speech, text, image), self.device)
+
+
+class FusionMixedPlan:
+    """A mixed batch's routing (mec_fusion_mixed_plan): host `present` (bitmask uint8 [B]), `route`
+    (ROUTE_* int32 [B]), `s_idx` / `t_idx` / `i_idx` / `att` (int32 [B]), `counts` = (ns, nt, ni), `n_att`,
+    `have_model`; `dev` holds s_idx | t_idx | i_idx | att as one int32 [4,B] device tensor."""
+
+    def __init__(self, present, have_model, route, idx, att, counts, n_att, dev):
+        self.present, self.have_model, self.route = present, bool(have_model), route
+        self.s_idx, self.t_idx, self.i_idx = idx
+        self.att, self.counts, self.n_att, self.dev = att, tuple(int(c) for c in counts), int(n_att), dev
+        self.B = int(present.size)
+
+    def rows(self, route):
+        """The samples on `route` (a _lib.ROUTE_* value), ascending."""
+        return np.flatnonzero(self.route == route)
+
+
+def fusion_mixed_plan(present, have_model: bool = True, device=None) -> FusionMixedPlan:
+    """present: a host bool / uint8 array [B,3] (speech, text, image) or a bitmask [B] (an or of
+    _lib.MOD_SPEECH / MOD_TEXT / MOD_IMAGE) -> the plan, its index arrays uploaded once to `device`.
+    have_model=False: no attention model, samples with all three modalities take the average."""
+    lib = _lib.load()
+    dev = require_gpu(device)
+    p = np.asarray(present)
+    if p.ndim == 2 and p.shape[1] == 3:
+        p = (p != 0).astype(np.uint8) @ np.array([1, 2, 4], np.uint8)
+    elif p.ndim != 1:
+        raise ValueError(f'present: shape {p.shape}, expected [B,3] flags or a [B] bitmask')
+    elif p.size and (p.min() < 0 or p.max() > 7):
+        raise ValueError('present: a bitmask entry outside [0, 7]')
+    p = np.ascontiguousarray(p, dtype=np.uint8)
+    B = int(p.size)
+    arr = np.full((5, B), -1, np.int32)  # s_idx | t_idx | i_idx | att | route
+    counts = np.zeros(3, np.int32)
+    ip = ctypes.POINTER(ctypes.c_int32)
+    a = [arr[k].ctypes.data_as(ip) for k in range(5)]
+    n_att = lib.mec_fusion_mixed_plan(p.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), B, int(bool(have_model)),
+                                      a[0], a[1], a[2], a[4], a[3], counts.ctypes.data_as(ip))
+    if n_att < 0:
+        _lib.check(n_att, 'mec_fusion_mixed_plan')
+    return FusionMixedPlan(p, have_model, arr[4], (arr[0], arr[1], arr[2]), arr[3], counts, n_att,
+                           torch.from_numpy(arr[:4].copy()).to(dev))
+
+
+def _fusion_mixed(lib, handle, plan, pairs, dev):
+    if not isinstance(plan, FusionMixedPlan):
+        raise TypeError(f'plan: expected a FusionMixedPlan (engine.fusion_mixed_plan), got {type(plan).__name__}')
+    B = plan.B
+    _check_tensor('plan.dev', plan.dev, torch.int32, (4, B), dev)
+    ptrs = []
+    for name, d, n, pair in zip(('speech', 'text', 'image'), (64, 768, 512), plan.counts, pairs):
+        if pair is None:
+            if n:
+                raise ValueError(f'{name}: None, but the plan has {n} samples with it')
+            ptrs.append((None, None))
+            continue
+        feat, pred = pair if handle is not None else (None, pair)
+        if feat is not None:
+            _check_tensor(f'{name} feat', feat, torch.float32, (n, d), dev)
+        _check_tensor(f'{name} probs', pred, torch.float32, (n, 7), dev)
+        ptrs.append((feat if n else None, pred if n else None))
+    fused = torch.empty((B, 7), dtype=torch.float64, device=dev)
+    logits, aw, dw = (torch.empty((B, k), dtype=torch.float32, device=dev) for k in (7, 3, 3))
+    if B == 0:
+        return fused, logits, aw, dw
+    (sf, sp), (tf, tp), (imf, ip) = ptrs
+    ns, nt, ni = plan.counts
+    args = _lib.FusionMixedArgs(s_feat=_ptr(sf), t_feat=_ptr(tf), i_feat=_ptr(imf), s_pred=_ptr(sp), t_pred=_ptr(tp),
+                                i_pred=_ptr(ip), ns=ns, nt=nt, ni=ni, s_idx=_ptr(plan.dev[0]), t_idx=_ptr(plan.dev[1]),
+                                i_idx=_ptr(plan.dev[2]), att=_ptr(plan.dev[3]), n_att=plan.n_att, B=B,
+                                fused=_ptr(fused), logits=_ptr(logits), attn_w=_ptr(aw), dec_w=_ptr(dw))
+    _lib.check(lib.mec_fusion_fwd_mixed(handle, ctypes.byref(args), _stream(dev)), 'mec_fusion_fwd_mixed')
+    plan.dev.record_stream(torch.cuda.current_stream(dev))
+    return fused, logits, aw, dw
+
+
+def fuse_mixed(plan, s_pred=None, t_pred=None, i_pred=None):
+    """`FusionHead.forward_mixed` without an attention model (the null handle; a plan made with
+    have_model=False): compact probs [ns,7] / [nt,7] / [ni,7] (None when the count is 0) ->
+    (fused f64 [B,7], logits, attn_w, dec_w), the last three all zeros. Samples with two or three
+    modalities take the float64 average."""
+    if isinstance(plan, FusionMixedPlan) and plan.have_model:
+        raise ValueError('fuse_mixed: the plan was made with have_model=True (FusionHead.forward_mixed takes it)')
+    return _fusion_mixed(_lib.load(), None, plan, (s_pred, t_pred, i_pred), plan.dev.device)
+
 
 def fuse_weighted(s=None, t=None, i=None, device=None) -> torch.Tensor:
     """Weighted-average fallback on the GPU (float64) -> [B,7] f64; None = missing modality."""
@@ -607,6 +704,7 @@ class FusedPipeline:
         self._text = (torch.cuda.Stream(device=self.device, priority=0 if image_priority else -1)
                       if (concurrent and (text_priority or image_priority)) else None)
         self._tuned = set()  # batch sizes B, or (B, packed rows Bp), whose GEMM shapes were autotuned (serially)
+        self._tuned_mixed = set()  # the same for forward_mixed: (text key, ni), the text key nt or (nt, Bp)
         self._last, self._since_check = None, 0
         if concurrent and precision == 'f16':
             # BERT FFN2 (M = 128 B, N = 768, K = 3072) on the 256 x 256 ping-pong tile beside the
@@ -639,7 +737,6 @@ class FusedPipeline:
         the text leg runs packed (TextEncoder.forward_packed) on the text stream. The plan's Bp sets
         BERT's GEMM shapes (M = 128 Bp), so the serial first-batch autotune rule applies per (B, Bp): the
         first batch of a Bp not seen with this B runs serially."""
-        main = torch.cuda.current_stream(self.device)
         B = int(ids.shape[0])
         if text_lens is None:
             text_fwd, key = (lambda: self.text.forward(ids, mask)), B
@@ -647,29 +744,51 @@ class FusedPipeline:
             text_lens = np.ascontiguousarray(text_lens, dtype=np.int32)
             key = (B, self.text.pack_plan(text_lens)[2])
             text_fwd = lambda: self.text.forward_packed(ids, mask, text_lens)  # noqa: E731
-        if not self.concurrent or key not in self._tuned:
+        (sf, sl, sp), (tf, tl, tp), (imf, il, ip), fstream = self._encoders(
+            key, self._tuned, lambda: self.speech.forward(x_speech), text_fwd, lambda: self.image.forward(gray),
+            (x_speech, gray), (ids, mask))
+        with torch.cuda.stream(fstream):
+            fl, fp, aw, dw = self.fusion.forward(sf, tf, imf, sp, tp, ip)
+            out = {'speech': (sf, sl, sp), 'text': (tf, tl, tp), 'image': (imf, il, ip),
+                   'fusion': (fl, fp, aw, dw)}
+            extra = epilogue(out) if epilogue is not None else None
+        self._record(out, ids, mask, gray, text_lens)
+        return out if epilogue is None else (out, extra)
+
+    def _record(self, out, ids, mask, gray, text_lens):
+        self._last = {'text': (ids, mask), 'image': (gray,), 'out': out}  # check() repairs this batch
+        if text_lens is not None:
+            self._last.update(text=(ids, mask, text_lens), text_method='forward_packed')
+        self._since_check += 1
+
+    def _encoders(self, key, tuned, speech_fwd, text_fwd, image_fwd, side_in, text_in):
+        """The three encoder legs of one batch on their streams -> (speech, text, image output tuples, the
+        stream the fusion runs on). `key` not in `tuned` (or concurrent=False): everything serially on the
+        caller's stream. side_in / text_in: the input tensors the side / text stream reads."""
+        main = torch.cuda.current_stream(self.device)
+        if not self.concurrent or key not in tuned:
             # a batch size not seen yet runs serially on one stream, so each new GEMM shape is
             # autotuned alone (not against the other encoder's kernels)
             for st in (self._side, self._text, self._tail):  # nothing else in flight while tuning
                 if st is not None:
                     main.wait_stream(st)
-            sf, sl, sp = self.speech.forward(x_speech)
+            sf, sl, sp = speech_fwd()
             tf, tl, tp = text_fwd()
-            imf, il, ip = self.image.forward(gray)
-            self._tuned.add(key)
+            imf, il, ip = image_fwd()
+            tuned.add(key)
             fstream = main
         else:
             side = self._side
             side.wait_stream(main)  # inputs were produced on the main stream
             with torch.cuda.stream(side):
-                sf, sl, sp = self.speech.forward(x_speech)
-                imf, il, ip = self.image.forward(gray)
+                sf, sl, sp = speech_fwd()
+                imf, il, ip = image_fwd()
             if self._text is not None:
                 tstream = self._text
                 tstream.wait_stream(main)
                 with torch.cuda.stream(tstream):
                     tf, tl, tp = text_fwd()
-                for t in (ids, mask):
+                for t in text_in:
                     t.record_stream(tstream)
                 if not self.pipelined:
                     main.wait_stream(tstream)
@@ -678,7 +797,7 @@ class FusedPipeline:
             else:
                 tstream = main
                 tf, tl, tp = text_fwd()
-            for t in (x_speech, gray):
+            for t in side_in:
                 t.record_stream(side)
             if self.pipelined:
                 fstream = self._tail
@@ -691,16 +810,43 @@ class FusedPipeline:
                 for t in (sf, sl, sp, imf, il, ip):
                     t.record_stream(main)
                 fstream = main
+        return (sf, sl, sp), (tf, tl, tp), (imf, il, ip), fstream
+
+    def forward_mixed(self, x_speech, ids, mask, gray, present, epilogue=None, text_lens=None):
+        """`forward` for a batch of B requests that each have any subset of the modalities. present: host
+        flags [B,3] or a bitmask [B] (engine.fusion_mixed_plan); x_speech f32 [ns,56], ids / mask int32
+        [nt,128], gray u8 [ni,48,48]: the compact rows of the samples that have each modality, in sample
+        order. Each encoder runs once over its rows (not at all when it has none: its outputs are empty
+        [0,d] tensors), on the streams `forward` uses; the fusion routes every sample as predict_multimodal
+        routes a request (FusionHead.forward_mixed). text_lens: the nt sentence lengths (the packed text
+        leg). The serial first-batch autotune rule applies per (text key, ni), the text key nt or (nt, Bp).
+        -> the dict `forward` returns with compact per-modality tuples, 'fusion': (fused f64 [B,7], logits,
+        attn_w, dec_w) and 'plan'."""
+        plan = fusion_mixed_plan(present, True, self.device)
+        ns, nt, ni = plan.counts
+        for name, t, n in (('x_speech', x_speech, ns), ('ids', ids, nt), ('mask', mask, nt), ('gray', gray, ni)):
+            if not isinstance(t, torch.Tensor) or t.dim() < 1 or int(t.shape[0]) != n:
+                raise ValueError(f'{name}: expected a tensor of {n} rows (the samples `present` gives this modality)')
+        if text_lens is None:
+            text_fwd, tkey = (lambda: self.text.forward(ids, mask)), nt
+        else:
+            text_lens = np.ascontiguousarray(text_lens, dtype=np.int32)
+            tkey = (nt, self.text.pack_plan(text_lens)[2])
+            text_fwd = lambda: self.text.forward_packed(ids, mask, text_lens)  # noqa: E731
+        empty = lambda d: lambda: (self.speech._empty(0, d), self.speech._empty(0, 7), self.speech._empty(0, 7))  # noqa: E731
+        s, t, i, fstream = self._encoders(
+            (tkey, ni), self._tuned_mixed,
+            (lambda: self.speech.forward(x_speech)) if ns else empty(64), text_fwd if nt else empty(768),
+            (lambda: self.image.forward(gray)) if ni else empty(512), (x_speech, gray), (ids, mask))
         with torch.cuda.stream(fstream):
-            fl, fp, aw, dw = self.fusion.forward(sf, tf, imf, sp, tp, ip)
-            out = {'speech': (sf, sl, sp), 'text': (tf, tl, tp), 'image': (imf, il, ip),
-                   'fusion': (fl, fp, aw, dw)}
+            out = {'speech': s, 'text': t, 'image': i, 'fusion': self._fuse_mixed(plan, s, t, i), 'plan': plan}
             extra = epilogue(out) if epilogue is not None else None
-        self._last = {'text': (ids, mask), 'image': (gray,), 'out': out}  # check() repairs this batch
-        if text_lens is not None:
-            self._last.update(text=(ids, mask, text_lens), text_method='forward_packed')
-        self._since_check += 1
+        self._record(out, ids, mask, gray, text_lens)
         return out if epilogue is None else (out, extra)
+
+    def _fuse_mixed(self, plan, s, t, i):
+        pair = lambda o, n: (o[0], o[2]) if n else None  # noqa: E731
+        return self.fusion.forward_mixed(plan, *(pair(o, n) for o, n in zip((s, t, i), plan.counts)))
 
     def wait(self, stream=None):
         """Make `stream` (default: the current one) wait for the last batch's fusion."""
@@ -729,7 +875,9 @@ class FusedPipeline:
         if redo:
             o = last['out']
             (sf, _, sp), (tf, _, tp), (imf, _, ip) = o['speech'], o['text'], o['image']
-            for d, r in zip(o['fusion'], self.fusion.forward(sf, tf, imf, sp, tp, ip)):
+            again = (self._fuse_mixed(o['plan'], o['speech'], o['text'], o['image']) if 'plan' in o
+                     else self.fusion.forward(sf, tf, imf, sp, tp, ip))
+            for d, r in zip(o['fusion'], again):
                 d.copy_(r)
             torch.cuda.synchronize(self.device)
         return redo
