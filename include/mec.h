@@ -329,6 +329,37 @@ int mec_fuse_weighted_f64(const double* s_probs, const double* t_probs, const do
 
 /* Kernel-level entry points (parity tests / microbenchmarks). */
 int mec_resize_u8(const uint8_t* in, int B, int H, int W, uint8_t* out, int OH, int OW, void* stream);
+
+/* PIL-exact bilinear resize of a ragged batch to 224 x 224 (csrc/resize.hip): what
+ *   rgb.resize((224, 224), Image.BILINEAR)   inference/image_inference.py (the reference's Resize((224,224)))
+ * gives, byte for byte, for every image of the domain
+ *   1 <= H <= 4096, 1 <= W <= 4096, H <= 100 W          (mec_resize_on_gpu(H, W) != 0)
+ * Pillow 12.2 resamples horizontally into a u8 intermediate, then vertically, and these kernels do the same;
+ * for H > 100 W (and H > 224) Pillow's bytes are those of the other order, which is not restated: such an
+ * image stays with the host.
+ *
+ * mec_resize_taps: Pillow's taps for one extent (precompute_coeffs + normalize_coeffs_8bpc, bilinear, in
+ * double on the host): output i sums n[i] source samples from xmin[i] on, times k[i * kmax + j] / 2^22; the
+ * taps past n[i] are 0. kmax >= 2 * ceil(max(in_size / out_size, 1)) + 1 (39 for 4096 -> 224). Host only: it
+ * needs no GPU.
+ *
+ * mec_resize_ragged_u8: image i is u8 [H_i, W_i, C] (hw[2 i], hw[2 i + 1]) at byte offs[i] of the device
+ * buffer src (src_bytes long); C is 1 or 3 for the whole batch. tmp (device, 4-byte aligned, tmp_bytes >= the
+ * sum of H_i * 224 * C) takes the horizontal pass' result; out (device) is u8 [B, 224, 224, C]. offs and hw
+ * are HOST arrays. Everything is checked on the host before any launch: a null pointer, B < 0, C, an image
+ * outside the domain or not inside src_bytes, a short tmp, B > 65535 return -1 with a message and launch
+ * nothing; B == 0 returns 0. The call builds (or takes from a bounded process-wide cache) the tap tables of the batch's
+ * extents and uploads them with the descriptors itself, from a staging buffer it owns and re-uses once the
+ * previous call's kernels have finished: it is asynchronous on `stream` but NOT capturable in a graph, and a
+ * call may wait on the host for the previous one. */
+int mec_resize_on_gpu(int H, int W);
+int mec_resize_taps(int in_size, int out_size, int32_t* xmin, int32_t* n, int32_t* k, int kmax);
+int mec_resize_ragged_u8(const uint8_t* src, const int64_t* offs, const int32_t* hw, int B, int C, size_t src_bytes,
+                         uint8_t* tmp, size_t tmp_bytes, uint8_t* out, void* stream);
+/* hipEvent timing of the two passes, process-wide (these calls have no handle): enable (on != 0) or disable
+ * and forget what was recorded; read the totals of the calls since, in ms, and forget them. */
+int mec_resize_prof_enable(int on);
+int mec_resize_prof_read(double* horizontal_ms, double* vertical_ms, int* count);
 /* C[M,N] = act(A[M,K] . B[N,K]^T + bias (+ R)); f16 operands, fp32 accumulate.
  * act: 0 none, 1 relu, 2 gelu(erf). Any of bias/R/C16/C32 may be NULL (not both outputs). */
 /* Split-f16 GEMM (the MEC_PREC_FP32X3 engine): A and B each an f16 hi plane with its lo plane

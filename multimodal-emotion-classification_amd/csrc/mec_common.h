@@ -66,6 +66,8 @@ enum KernelTag : int {
   TAG_LSTM_REC1 = 17,
   TAG_LSTM_REC2 = 18,
   TAG_LSTM_HEAD = 19,
+  TAG_RESIZE_H = 20,  // resize.hip: the ragged resize's two passes (mec_resize_prof_*)
+  TAG_RESIZE_V = 21,
 };
 
 // Tuning knobs (mec_set_option / mec_model_set_option, include/mec.h). Every model handle

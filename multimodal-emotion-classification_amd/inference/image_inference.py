@@ -9,6 +9,11 @@ torchvision makes) and uploaded as u8 224x224, gray (1 channel) or RGB (3 channe
 labels are Config.EMOTIONS[argmax] exactly like the reference (:121-123), including its
 class-order quirk against ImageFolder's alphabetical training order.
 
+With resize='gpu' (opt-in) the host keeps the decoding, the RGB conversion and the gray test, and an image of
+any size inside mec.image.resize_on_gpu's domain is uploaded as it is and resized on the GPU to PIL's bytes
+(csrc/resize.hip), so the results equal resize='host''s bit for bit; predict_arrays / extract_features_arrays
+take a batch of in-memory u8 arrays of any sizes.
+
 Added beyond the reference: predict_array(u8 image) and predict_batch(u8 [B,48,48]), and
 `backbone='mobilenet_v2'` (README.md:13 names MobileNetV2 as the image model; the reference
 code builds ResNet50): the same transform, head, feature and result dicts on a
@@ -22,27 +27,54 @@ import numpy as np
 from config import Config
 from mec import checkpoints, engine
 from mec._lib import MecError
+from mec.image import resize_on_gpu
 
 
-def _to_model_input(image) -> np.ndarray:
-    """PIL image -> u8 array [H,W,C] in one of the shapes the HIP path takes."""
+def _route(image, resize: str = 'host'):
+    """PIL image -> (u8 array [H,W,C], ragged). ragged False: the array has one of the shapes the HIP path
+    takes, (48,48,1) or PIL-resized (224,224,C). ragged True (resize='gpu' only): the image's own pixels,
+    gray (C = 1) or RGB (C = 3), to be resized on the GPU (engine.resize_ragged); only an image inside
+    mec.image.resize_on_gpu's domain is routed there. The gray test runs on the original pixels either way."""
     from PIL import Image
     rgb = image.convert('RGB')  # reference :112
     a = np.asarray(rgb, dtype=np.uint8)
     gray = bool((a[..., 0] == a[..., 1]).all() and (a[..., 0] == a[..., 2]).all())
     if gray and a.shape[:2] == (48, 48):
-        return np.ascontiguousarray(a[..., :1])  # GPU resize path
+        return np.ascontiguousarray(a[..., :1]), False  # GPU resize path
+    if resize == 'gpu' and resize_on_gpu(a.shape[0], a.shape[1]):
+        return np.ascontiguousarray(a[..., :1] if gray else a), True
     r = np.asarray(rgb.resize((224, 224), Image.BILINEAR), dtype=np.uint8)  # Resize((224,224))
-    return np.ascontiguousarray(r[..., :1] if gray else r)
+    return np.ascontiguousarray(r[..., :1] if gray else r), False
+
+
+def _to_model_input(image) -> np.ndarray:
+    """PIL image -> u8 array [H,W,C] in one of the shapes the HIP path takes."""
+    return _route(image, 'host')[0]
+
+
+def _as_image(arr):
+    """u8 array [H,W] / [H,W,1] (gray) or [H,W,3] (RGB) -> PIL image."""
+    from PIL import Image
+    a = np.asarray(arr, np.uint8)
+    if a.ndim == 3 and a.shape[2] == 1:
+        a = a[..., 0]
+    if a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] != 3):
+        raise ValueError(f'image array: shape {a.shape} is not [H,W], [H,W,1] or [H,W,3]')
+    return Image.fromarray(np.ascontiguousarray(a), 'L' if a.ndim == 2 else 'RGB')
 
 
 _KINDS = {'resnet50': 'image', 'mobilenet_v2': 'image_mbv2'}
 
 
 class ImageInference:
-    def __init__(self, weights=None, seed=None, device=None, backbone='resnet50', precision=None):
+    def __init__(self, weights=None, seed=None, device=None, backbone='resnet50', precision=None, resize='host'):
         if backbone not in _KINDS:
             raise ValueError(f'backbone must be one of {sorted(_KINDS)}')
+        if resize not in ('host', 'gpu'):
+            raise ValueError("resize must be 'host' or 'gpu'")
+        # 'gpu': an image that is not a 48x48 gray face and lies in the GPU resize's domain is uploaded as it
+        # is and resized there (csrc/resize.hip), with PIL's bytes and so with 'host''s results bit for bit
+        self.resize = resize
         self.emotions = Config.EMOTIONS
         self.backbone = backbone
         self.model = None
@@ -65,6 +97,44 @@ class ImageInference:
         feat, logits, probs = self.model.checked('forward_u8', x)
         return feat.cpu().numpy()[0], probs.cpu().numpy()[0]
 
+    def forward_routed(self, items):
+        """items: a list of `_route` results -> (feat [n,512], probs [n,7]) device tensors in the list's order.
+        One forward per model-input shape, (48,48,1) / (224,224,1) / (224,224,3), as a batch of PIL-resized
+        images is grouped: a shape's ragged images are resized in one call (ImageEncoder.forward_ragged when
+        the group holds nothing else) and stand in the group's batch where PIL's results would, so both
+        settings of `resize` run the same forwards on the same bytes."""
+        import torch
+        dev = self.device
+        at = lambda rows: torch.tensor(rows, dtype=torch.int64, device=dev)  # noqa: E731
+        groups = {}  # model-input shape -> [rows, host arrays, their slots, ragged arrays, their slots]
+        for row, (arr, ragged) in enumerate(items):
+            g = groups.setdefault((224, 224, arr.shape[2]) if ragged else arr.shape, [[], [], [], [], []])
+            (g[3] if ragged else g[1]).append(arr)
+            (g[4] if ragged else g[2]).append(len(g[0]))
+            g[0].append(row)
+        feat = torch.empty((len(items), 512), dtype=torch.float32, device=dev)
+        probs = torch.empty((len(items), 7), dtype=torch.float32, device=dev)
+        for shape, (rows, host, host_at, ragged, ragged_at) in groups.items():
+            if not ragged:
+                f, _, p = self.model.checked('forward_u8', engine.to_device(np.stack(host), dev))
+            elif not host:
+                f, _, p = self.model.checked('forward_ragged', ragged)
+            else:
+                x = torch.empty((len(rows),) + shape, dtype=torch.uint8, device=dev)
+                x.index_copy_(0, at(ragged_at), engine.resize_ragged(ragged, dev))
+                x.index_copy_(0, at(host_at), engine.to_device(np.stack(host), dev))
+                f, _, p = self.model.checked('forward_u8', x)
+            feat.index_copy_(0, at(rows), f)
+            probs.index_copy_(0, at(rows), p)
+        return feat, probs
+
+    def _forward_image(self, image):
+        arr, ragged = _route(image, self.resize)
+        if not ragged:
+            return self._forward(arr)
+        feat, probs = self.forward_routed([(arr, True)])
+        return feat.cpu().numpy()[0], probs.cpu().numpy()[0]
+
     @staticmethod
     def _as_dict(emotions, probs: np.ndarray) -> Dict:
         idx = int(np.argmax(probs))
@@ -77,14 +147,31 @@ class ImageInference:
             a = a[..., None]
         return self._as_dict(self.emotions, self._forward(a)[1])
 
+    def extract_features_arrays(self, arrays):
+        """u8 images of any sizes, [H,W] / [H,W,1] gray or [H,W,3] RGB -> (feat [n,512], probs [n,7]) numpy,
+        each image treated as `extract_features` treats a file that decodes to it (RGB conversion, gray test,
+        Resize((224,224))), the batch run as one forward per model-input shape. With resize='gpu' the images
+        of the GPU resize's domain are uploaded unresized in one copy and resized there."""
+        if self.model is None:
+            raise RuntimeError('image model not loaded')
+        items = [_route(_as_image(a), self.resize) for a in arrays]
+        if not items:
+            return np.zeros((0, 512), np.float32), np.zeros((0, 7), np.float32)
+        feat, probs = self.forward_routed(items)
+        return feat.cpu().numpy(), probs.cpu().numpy()
+
+    def predict_arrays(self, arrays):
+        """`extract_features_arrays`' probabilities as one result dict per image."""
+        return [self._as_dict(self.emotions, p) for p in self.extract_features_arrays(arrays)[1]]
+
     def predict(self, image_file_path: str) -> Dict:
         if self.model is None:
             return self._fallback()
         try:
             from PIL import Image
             with Image.open(image_file_path) as im:
-                arr = _to_model_input(im)
-            return self._as_dict(self.emotions, self._forward(arr)[1])
+                feat_probs = self._forward_image(im)
+            return self._as_dict(self.emotions, feat_probs[1])
         except MecError:
             raise  # a failing HIP kernel is never hidden behind the fallback
         except Exception as e:
@@ -97,8 +184,7 @@ class ImageInference:
             return None, None
         from PIL import Image
         with Image.open(image_file_path) as im:
-            arr = _to_model_input(im)
-        return self._forward(arr)
+            return self._forward_image(im)
 
     def predict_batch(self, gray):
         """gray: device u8 [B,48,48] -> (feat [B,512], logits [B,7], probs [B,7]). Asynchronous on the

@@ -27,20 +27,21 @@ from mec._lib import MecError
 from inference import speech_inference as _speech
 from inference.speech_inference import SpeechInference
 from inference.text_inference import TextInference
-from inference.image_inference import ImageInference, _to_model_input
+from inference.image_inference import ImageInference, _route
 
 _MODS = ('speech', 'text', 'image')
 
 
 class MultimodalFusion:
-    def __init__(self, weights=None, seed=None, device=None, precision=None):
+    def __init__(self, weights=None, seed=None, device=None, precision=None, image_resize='host'):
         weights = weights or {}
         self.emotions = Config.EMOTIONS
         self.weights = [0.3, 0.35, 0.35]  # speech, text, image (reference :23)
         self.fusion_model = None
         self.speech_inference = SpeechInference(weights.get('speech'), seed, device)
         self.text_inference = TextInference(weights.get('text'), seed, device, precision=precision)
-        self.image_inference = ImageInference(weights.get('image'), seed, device, precision=precision)
+        self.image_inference = ImageInference(weights.get('image'), seed, device, precision=precision,
+                                              resize=image_resize)
         w = checkpoints.resolve('fusion', weights.get('fusion'), seed)
         if w is not None:
             self.fusion_model = engine.FusionHead(w, device=device)  # raises MecError without HIP/GPU
@@ -163,7 +164,7 @@ class MultimodalFusion:
         # ---- host: decode every file first
         ap = _speech._preprocessing() if present[:, 0].any() else None
         waves, wave_at, hostf, hostf_at = [], [], [], []  # compact speech rows: GPU features / host features
-        images = {}  # input shape -> (arrays, compact image rows)
+        images = []  # per compact image row: (array, resized on the GPU?) (image_inference._route)
         ns = ni = 0
         for b, (a, _, i) in enumerate(reqs):
             if a is not None:
@@ -182,12 +183,9 @@ class MultimodalFusion:
                 try:
                     from PIL import Image
                     with Image.open(i) as im:
-                        arr = _to_model_input(im)
+                        images.append(_route(im, self.image_inference.resize))
                 except Exception as e:
                     raise ValueError(f'request {b}: cannot read image {i!r}: {e}') from e
-                arrs, at = images.setdefault(arr.shape, ([], []))
-                arrs.append(arr)
-                at.append(ni)
                 ni += 1
         texts = [t for _, t, _ in reqs if t is not None]
         dev = self.device
@@ -210,13 +208,9 @@ class MultimodalFusion:
             tf, _, tp = self.text_inference.model.checked('forward', ids, mask)
             text = (tf, tp)
         if ni:
-            imf = torch.empty((ni, 512), dtype=torch.float32, device=dev)
-            ip = torch.empty((ni, 7), dtype=torch.float32, device=dev)
-            for arrs, at in images.values():  # one forward per input shape, placed in compact order
-                f, _, p = self.image_inference.model.checked('forward_u8', engine.to_device(np.stack(arrs), dev))
-                imf.index_copy_(0, at_dev(at), f)
-                ip.index_copy_(0, at_dev(at), p)
-            image = (imf, ip)
+            # one forward per model-input shape, placed in compact order; with image_resize='gpu' the images
+            # the GPU resizes are grouped by channel count and resized in one call per group
+            image = self.image_inference.forward_routed(images)
         # ---- one routed fusion call
         plan = engine.fusion_mixed_plan(present, self.fusion_model is not None, dev)
         if self.fusion_model is not None:

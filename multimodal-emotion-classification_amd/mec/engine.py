@@ -13,7 +13,7 @@ import threading
 import numpy as np
 import torch
 
-from . import _lib, synthetic, tokenize as _tok
+from . import _lib, image as _image, synthetic, tokenize as _tok
 from ._lib import MecError
 
 TAG_BERT_FFN2 = 5  # launch class of BERT's FFN2 GEMM (mec_common.h Tag)
@@ -469,6 +469,71 @@ class ImageEncoder(HipModel):
             _lib.check(self.lib.mec_image_fwd_u8(self.handle, _ptr(img), B, H, W, C, _ptr(feat), _ptr(logits),
                                                  _ptr(probs), _stream(self.device)), 'mec_image_fwd_u8')
         return feat, logits, probs
+
+    def forward_ragged(self, arrays):
+        """arrays: u8 images [H,W,C] of any sizes inside the GPU resize's domain, one C (1 or 3) for all:
+        resized on the GPU as PIL resizes them (resize_ragged), then forward_u8."""
+        return self.forward_u8(resize_ragged(arrays, self.device))
+
+
+def resize_ragged(arrays, device=None, channels: int = 3) -> torch.Tensor:
+    """A list of u8 images [H,W,C] (or [H,W]) that share one C in {1, 3} -> u8 [B,224,224,C] on the device,
+    each image resized as PIL's `resize((224, 224), Image.BILINEAR)` resizes it, byte for byte
+    (mec_resize_ragged_u8; csrc/resize.hip). Every image must lie in the domain mec.image.resize_on_gpu
+    states (ValueError otherwise: the caller routes the others to the host). The images are packed into one
+    pinned staging buffer and uploaded in one copy; the intermediate and the result are torch allocations.
+    Asynchronous on the current stream. `channels` only gives an empty list its C."""
+    lib = _lib.load()
+    dev = require_gpu(device)
+    arrs = []
+    for i, a in enumerate(arrays):
+        a = np.asarray(a)
+        if a.ndim == 2:
+            a = a[..., None]
+        if a.dtype != np.uint8 or a.ndim != 3:
+            raise TypeError(f'image {i}: expected a u8 array [H,W,C], got {a.dtype} {a.shape}')
+        arrs.append(a)
+    C = arrs[0].shape[2] if arrs else int(channels)
+    if C not in (1, 3):
+        raise ValueError(f'C must be 1 or 3, got {C}')
+    for i, a in enumerate(arrs):
+        if a.shape[2] != C:
+            raise ValueError(f'image {i}: {a.shape[2]} channels in a batch of C = {C}')
+        if not _image.resize_on_gpu(a.shape[0], a.shape[1]):
+            raise ValueError(f'image {i}: {a.shape[0]} x {a.shape[1]} is outside the GPU resize\'s domain')
+    B = len(arrs)
+    out = torch.empty((B, _image.OUT, _image.OUT, C), dtype=torch.uint8, device=dev)
+    if B == 0:
+        return out
+    hw = np.array([a.shape[:2] for a in arrs], np.int32).reshape(B, 2)
+    size = hw[:, 0].astype(np.int64) * hw[:, 1] * C
+    offs = np.zeros(B, np.int64)
+    offs[1:] = np.cumsum((size[:-1] + 15) // 16 * 16)  # every image starts on a 16-byte boundary
+    total = int(offs[-1] + size[-1])
+    stage = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+    view = stage.numpy()
+    for a, o, n in zip(arrs, offs, size):
+        view[o:o + n] = a.reshape(-1)
+    tmp_bytes = int(hw[:, 0].astype(np.int64).sum()) * _image.OUT * C
+    with torch.cuda.device(dev):
+        src = stage.to(dev, non_blocking=True)
+        tmp = torch.empty(tmp_bytes, dtype=torch.uint8, device=dev)
+        _lib.check(lib.mec_resize_ragged_u8(_ptr(src), offs.ctypes.data, hw.ctypes.data, B, C, total, _ptr(tmp),
+                                            tmp_bytes, _ptr(out), _stream(dev)), 'mec_resize_ragged_u8')
+    return out
+
+
+def resize_prof(on: bool):
+    """Switch the hipEvent timing of the ragged resize's two kernels on or off (process-wide)."""
+    _lib.check(_lib.load().mec_resize_prof_enable(int(bool(on))), 'mec_resize_prof_enable')
+
+
+def resize_prof_read():
+    """(horizontal ms, vertical ms, calls) since the last read or enable; synchronizes on the events."""
+    h, v, n = ctypes.c_double(), ctypes.c_double(), ctypes.c_int()
+    _lib.check(_lib.load().mec_resize_prof_read(ctypes.byref(h), ctypes.byref(v), ctypes.byref(n)),
+               'mec_resize_prof_read')
+    return h.value, v.value, n.value
 
 
 class MobileNetImageEncoder(ImageEncoder):
