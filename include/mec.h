@@ -360,6 +360,43 @@ int mec_resize_ragged_u8(const uint8_t* src, const int64_t* offs, const int32_t*
  * and forget what was recorded; read the totals of the calls since, in ms, and forget them. */
 int mec_resize_prof_enable(int on);
 int mec_resize_prof_read(double* horizontal_ms, double* vertical_ms, int* count);
+
+/* Mode conversion and the gray test of a ragged batch in native pixel formats (csrc/image_canon.hip): what
+ *   rgb = image.convert('RGB'); gray = (R == G).all() and (R == B).all()   inference/image_inference.py _route
+ * give for Pillow's modes L, LA, RGB, RGBA and P, byte for byte: L and LA replicate L, RGBA drops alpha, P looks
+ * each index up in getpalette('RGB') zero-padded to 256 entries (an RGBA palette or info['transparency'] does
+ * not change the lookup). Image i is u8 [H_i, W_i, bpp(fmt[i])] at byte offs[i] of the device buffer src
+ * (src_bytes long), packed as mec_resize_ragged_u8 takes it; any byte alignment. A MEC_PIX_P image names its
+ * palette, 768 bytes (256 RGB entries, zero-padded by the caller) in the same buffer, by pal_off[i]; every other
+ * format has pal_off[i] == -1. Images may share a palette. The domain is mec_resize_on_gpu's.
+ *
+ * mec_image_gray_ragged_u8: gray (device int32[B]) takes 1 where every pixel of image i has R == G == B after
+ * conversion, else 0. L and LA are gray by definition; a P image is gray when no index byte selects a coloured
+ * palette entry (an unused coloured entry does not count); RGBA's alpha does not count.
+ *
+ * mec_image_canon_ragged_u8: c_out[i] == 3 writes image i converted to RGB, u8 [H_i, W_i, 3], at dst +
+ * dst_offs[i]; 1 writes its R channel, u8 [H_i, W_i, 1] (for an image known to be gray; L -> 1 is a copy, which
+ * gathers 48 x 48 faces into one batch); 0 writes nothing. dst (device, 16-byte aligned, dst_bytes long) may
+ * lie in the allocation of src, so that one mec_resize_ragged_u8 call reads untouched and converted images
+ * through one pointer: a written range may overlap no image or palette of the batch (whatever its c_out) and
+ * no other written range. dst_offs are multiples of 16. Nothing outside the written ranges is touched.
+ *
+ * offs, hw, fmt, pal_off, c_out and dst_offs are HOST arrays. Everything is checked on the host before any
+ * launch: a null pointer, B < 0, B > 65535, an unknown fmt, an image outside the domain, an image or palette
+ * not inside src_bytes, a P image without a palette or a palette on another format, c_out outside {0, 1, 3}, a
+ * misaligned or out-of-range dst_off and overlapping ranges return -1 with a message and launch nothing; B == 0
+ * returns 0. Each call uploads its descriptors itself from a staging buffer it owns and re-uses once the previous
+ * call's kernels have finished: asynchronous on `stream`, NOT capturable in a graph. */
+enum { MEC_PIX_L = 0, MEC_PIX_LA = 1, MEC_PIX_RGB = 2, MEC_PIX_RGBA = 3, MEC_PIX_P = 4 };
+int mec_image_gray_ragged_u8(const uint8_t* src, const int64_t* offs, const int32_t* hw, const int32_t* fmt,
+                             const int64_t* pal_off, int B, size_t src_bytes, int32_t* gray, void* stream);
+int mec_image_canon_ragged_u8(const uint8_t* src, const int64_t* offs, const int32_t* hw, const int32_t* fmt,
+                              const int64_t* pal_off, const int32_t* c_out, const int64_t* dst_offs, int B,
+                              size_t src_bytes, uint8_t* dst, size_t dst_bytes, void* stream);
+/* hipEvent timing of the gray kernel and the conversion kernel, process-wide, as mec_resize_prof_*; a call that
+ * launches no such kernel (only L / LA images; every c_out 0) is not counted. */
+int mec_image_canon_prof_enable(int on);
+int mec_image_canon_prof_read(double* gray_ms, int* gray_count, double* canon_ms, int* canon_count);
 /* C[M,N] = act(A[M,K] . B[N,K]^T + bias (+ R)); f16 operands, fp32 accumulate.
  * act: 0 none, 1 relu, 2 gelu(erf). Any of bias/R/C16/C32 may be NULL (not both outputs). */
 /* Split-f16 GEMM (the MEC_PREC_FP32X3 engine): A and B each an f16 hi plane with its lo plane

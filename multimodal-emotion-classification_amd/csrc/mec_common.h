@@ -68,6 +68,8 @@ enum KernelTag : int {
   TAG_LSTM_HEAD = 19,
   TAG_RESIZE_H = 20,  // resize.hip: the ragged resize's two passes (mec_resize_prof_*)
   TAG_RESIZE_V = 21,
+  TAG_CANON_GRAY = 22,  // image_canon.hip: the gray test and the conversion (mec_image_canon_prof_*)
+  TAG_CANON_PIX = 23,
 };
 
 // Tuning knobs (mec_set_option / mec_model_set_option, include/mec.h). Every model handle

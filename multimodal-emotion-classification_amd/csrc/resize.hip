@@ -10,6 +10,7 @@
 
 #include "mec.h"
 #include "mec_common.h"
+#include "ragged_stage.h"
 
 namespace mec {
 namespace rr {
@@ -184,42 +185,14 @@ __global__ __launch_bounds__(256) void vertical_kernel(const uint8_t* __restrict
   o[3] = (uint8_t)clip8(a3);
 }
 
-// The batch's descriptors and tables: one pinned host image, one device copy, per device. A call waits for the
-// previous call's kernels on that device (the event) before it overwrites either, so calls on any streams
-// are safe; the kernels are short. Never freed (process lifetime, like the 48 x 48 path's table).
-struct State {
-  void* host = nullptr;
-  void* dev = nullptr;
-  size_t bytes = 0;
-  hipEvent_t done = nullptr;
-  bool pending = false;
-};
+// The batch's descriptors and tables (ragged_stage.h), per device.
+using State = StageBuf;
 std::mutex g_mu;
 std::map<int, State> g_state;
 // mec_resize_prof_*: TAG_RESIZE_H / TAG_RESIZE_V. Never destroyed: a static's destructor would destroy events
 // after the HIP runtime has shut down.
 Prof& g_prof_h = *new Prof;
 Prof& g_prof_v = *new Prof;
-
-int ensure(State& st, size_t bytes) {
-  if (!st.done) MEC_HIP(hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
-  if (st.pending) {
-    MEC_HIP(hipEventSynchronize(st.done));
-    st.pending = false;
-  }
-  if (bytes <= st.bytes) return 0;
-  if (st.host) (void)hipHostFree(st.host);
-  if (st.dev) (void)hipFree(st.dev);
-  st.host = st.dev = nullptr;
-  st.bytes = 0;
-  const size_t cap = std::max(bytes * 2, (size_t)1 << 16);
-  MEC_HIP(hipHostMalloc(&st.host, cap, hipHostMallocDefault));
-  MEC_HIP(hipMalloc(&st.dev, cap));
-  st.bytes = cap;
-  return 0;
-}
-
-size_t pad16(size_t n) { return (n + 15) & ~(size_t)15; }
 
 bool on_gpu(long long H, long long W) {
   return H >= 1 && H <= kMaxSide && W >= 1 && W <= kMaxSide && H <= 100 * W;

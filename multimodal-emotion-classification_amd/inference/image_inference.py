@@ -14,6 +14,11 @@ any size inside mec.image.resize_on_gpu's domain is uploaded as it is and resize
 (csrc/resize.hip), so the results equal resize='host''s bit for bit; predict_arrays / extract_features_arrays
 take a batch of in-memory u8 arrays of any sizes.
 
+With convert='gpu' (opt-in, needs resize='gpu') the host keeps only the decoding: an image of mode L, LA, RGB,
+RGBA or P inside that domain is uploaded in its native pixel format, and the RGB conversion, the gray test and
+the channel selection run on the GPU as well (csrc/image_canon.hip, engine.ingest_ragged), again with 'host''s
+bytes; every other mode or size takes the path above.
+
 Added beyond the reference: predict_array(u8 image) and predict_batch(u8 [B,48,48]), and
 `backbone='mobilenet_v2'` (README.md:13 names MobileNetV2 as the image model; the reference
 code builds ResNet50): the same transform, head, feature and result dicts on a
@@ -27,7 +32,7 @@ import numpy as np
 from config import Config
 from mec import checkpoints, engine
 from mec._lib import MecError
-from mec.image import resize_on_gpu
+from mec.image import PIX_L, PIX_RGB, native_pixels, resize_on_gpu
 
 
 def _route(image, resize: str = 'host'):
@@ -63,15 +68,29 @@ def _as_image(arr):
     return Image.fromarray(np.ascontiguousarray(a), 'L' if a.ndim == 2 else 'RGB')
 
 
+class Native(tuple):
+    """(pixels as decoded, mec.image.PIX_* format, palette or None): an image that convert='gpu' hands to
+    engine.ingest_ragged unconverted, where a `_route` result would stand."""
+
+
 _KINDS = {'resnet50': 'image', 'mobilenet_v2': 'image_mbv2'}
 
 
 class ImageInference:
-    def __init__(self, weights=None, seed=None, device=None, backbone='resnet50', precision=None, resize='host'):
+    def __init__(self, weights=None, seed=None, device=None, backbone='resnet50', precision=None, resize='host',
+                 convert='host'):
         if backbone not in _KINDS:
             raise ValueError(f'backbone must be one of {sorted(_KINDS)}')
         if resize not in ('host', 'gpu'):
             raise ValueError("resize must be 'host' or 'gpu'")
+        if convert not in ('host', 'gpu'):
+            raise ValueError("convert must be 'host' or 'gpu'")
+        if convert == 'gpu' and resize != 'gpu':
+            raise ValueError("convert='gpu' requires resize='gpu'")
+        # 'gpu': an image of mode L, LA, RGB, RGBA or P inside the GPU resize's domain is uploaded as decoded; the
+        # RGB conversion, the gray test and the channel selection run there too (csrc/image_canon.hip), with
+        # 'host''s bytes and so with its results bit for bit
+        self.convert = convert
         # 'gpu': an image that is not a 48x48 gray face and lies in the GPU resize's domain is uploaded as it
         # is and resized there (csrc/resize.hip), with PIL's bytes and so with 'host''s results bit for bit
         self.resize = resize
@@ -98,12 +117,15 @@ class ImageInference:
         return feat.cpu().numpy()[0], probs.cpu().numpy()[0]
 
     def forward_routed(self, items):
-        """items: a list of `_route` results -> (feat [n,512], probs [n,7]) device tensors in the list's order.
+        """items: a list of `_route` results (`route` results: with `Native` items among them the list takes
+        `_forward_ingested`, which builds the same batches) -> (feat [n,512], probs [n,7]) device tensors in the list's order.
         One forward per model-input shape, (48,48,1) / (224,224,1) / (224,224,3), as a batch of PIL-resized
         images is grouped: a shape's ragged images are resized in one call (ImageEncoder.forward_ragged when
         the group holds nothing else) and stand in the group's batch where PIL's results would, so both
         settings of `resize` run the same forwards on the same bytes."""
         import torch
+        if any(isinstance(it, Native) for it in items):
+            return self._forward_ingested(items)
         dev = self.device
         at = lambda rows: torch.tensor(rows, dtype=torch.int64, device=dev)  # noqa: E731
         groups = {}  # model-input shape -> [rows, host arrays, their slots, ragged arrays, their slots]
@@ -128,12 +150,77 @@ class ImageInference:
             probs.index_copy_(0, at(rows), p)
         return feat, probs
 
+    def _convert_on_gpu(self) -> bool:
+        return self.convert == 'gpu' and self.resize == 'gpu'
+
+    def route(self, image):
+        """PIL image -> an item of `forward_routed`: with convert='gpu' a `Native` for an image the GPU ingest
+        covers (mec.image.native_pixels: no conversion and no gray test on the host), else `_route`'s result."""
+        if self._convert_on_gpu():
+            native = native_pixels(image)
+            if native is not None:
+                return Native(native)
+        return _route(image, self.resize)
+
+    def route_array(self, arr):
+        """u8 array [H,W] / [H,W,1] / [H,W,3] -> an item of `forward_routed`; with convert='gpu' an array inside
+        the GPU resize's domain goes on as L / RGB pixels without a PIL image being built."""
+        if not self._convert_on_gpu():
+            return _route(_as_image(arr), self.resize)
+        a = np.asarray(arr, np.uint8)
+        if a.ndim == 3 and a.shape[2] == 1:
+            a = a[..., 0]
+        if a.ndim in (2, 3) and (a.ndim == 2 or a.shape[2] == 3) and resize_on_gpu(a.shape[0], a.shape[1]):
+            return Native((a, PIX_L if a.ndim == 2 else PIX_RGB, None))
+        return _route(_as_image(a), self.resize)  # raises for a shape that is no image's
+
+    def _forward_ingested(self, items):
+        """`forward_routed` for a list that holds `Native` items: they, and the `_route` results still to be
+        resized (L or RGB pixels by then), go through one engine.ingest_ragged call; its three batches and the
+        host-made arrays are merged per model-input shape in ascending row order, so every forward sees the batch
+        convert='host' builds."""
+        import torch
+        dev = self.device
+        at = lambda rows: torch.tensor(rows, dtype=torch.int64, device=dev)  # noqa: E731
+        shapes = ((48, 48, 1), (224, 224, 1), (224, 224, 3))
+        host = {s: ([], []) for s in shapes}  # model-input shape -> rows, host arrays
+        native, native_rows = [], []
+        for row, it in enumerate(items):
+            if isinstance(it, Native):
+                native.append(tuple(it))
+            elif it[1]:
+                native.append((it[0], PIX_L if it[0].shape[2] == 1 else PIX_RGB, None))
+            else:
+                host[it[0].shape][0].append(row)
+                host[it[0].shape][1].append(it[0])
+                continue
+            native_rows.append(row)
+        _, groups = engine.ingest_ragged(native, dev)
+        feat = torch.empty((len(items), 512), dtype=torch.float32, device=dev)
+        probs = torch.empty((len(items), 7), dtype=torch.float32, device=dev)
+        for shape, (x, local) in zip(shapes, groups):
+            grows, (hrows, harrs) = [native_rows[j] for j in local], host[shape]
+            rows = sorted(grows + hrows)
+            if not rows:
+                continue
+            if hrows:
+                slot = {r: k for k, r in enumerate(rows)}
+                merged = torch.empty((len(rows),) + shape, dtype=torch.uint8, device=dev)
+                if grows:
+                    merged.index_copy_(0, at([slot[r] for r in grows]), x)
+                merged.index_copy_(0, at([slot[r] for r in hrows]), engine.to_device(np.stack(harrs), dev))
+                x = merged
+            f, _, p = self.model.checked('forward_u8', x)
+            feat.index_copy_(0, at(rows), f)
+            probs.index_copy_(0, at(rows), p)
+        return feat, probs
+
     def _forward_image(self, image):
-        arr, ragged = _route(image, self.resize)
-        if not ragged:
-            return self._forward(arr)
-        feat, probs = self.forward_routed([(arr, True)])
-        return feat.cpu().numpy()[0], probs.cpu().numpy()[0]
+        item = self.route(image)
+        if isinstance(item, Native) or item[1]:
+            feat, probs = self.forward_routed([item])
+            return feat.cpu().numpy()[0], probs.cpu().numpy()[0]
+        return self._forward(item[0])
 
     @staticmethod
     def _as_dict(emotions, probs: np.ndarray) -> Dict:
@@ -151,10 +238,11 @@ class ImageInference:
         """u8 images of any sizes, [H,W] / [H,W,1] gray or [H,W,3] RGB -> (feat [n,512], probs [n,7]) numpy,
         each image treated as `extract_features` treats a file that decodes to it (RGB conversion, gray test,
         Resize((224,224))), the batch run as one forward per model-input shape. With resize='gpu' the images
-        of the GPU resize's domain are uploaded unresized in one copy and resized there."""
+        of the GPU resize's domain are uploaded unresized in one copy and resized there; with convert='gpu' they are
+        not converted or compared on the host either (`route_array`)."""
         if self.model is None:
             raise RuntimeError('image model not loaded')
-        items = [_route(_as_image(a), self.resize) for a in arrays]
+        items = [self.route_array(a) for a in arrays]
         if not items:
             return np.zeros((0, 512), np.float32), np.zeros((0, 7), np.float32)
         feat, probs = self.forward_routed(items)

@@ -27,13 +27,14 @@ from mec._lib import MecError
 from inference import speech_inference as _speech
 from inference.speech_inference import SpeechInference
 from inference.text_inference import TextInference
-from inference.image_inference import ImageInference, _route
+from inference.image_inference import ImageInference
 
 _MODS = ('speech', 'text', 'image')
 
 
 class MultimodalFusion:
-    def __init__(self, weights=None, seed=None, device=None, precision=None, image_resize='host'):
+    def __init__(self, weights=None, seed=None, device=None, precision=None, image_resize='host',
+                 image_convert='host'):
         weights = weights or {}
         self.emotions = Config.EMOTIONS
         self.weights = [0.3, 0.35, 0.35]  # speech, text, image (reference :23)
@@ -41,7 +42,7 @@ class MultimodalFusion:
         self.speech_inference = SpeechInference(weights.get('speech'), seed, device)
         self.text_inference = TextInference(weights.get('text'), seed, device, precision=precision)
         self.image_inference = ImageInference(weights.get('image'), seed, device, precision=precision,
-                                              resize=image_resize)
+                                              resize=image_resize, convert=image_convert)
         w = checkpoints.resolve('fusion', weights.get('fusion'), seed)
         if w is not None:
             self.fusion_model = engine.FusionHead(w, device=device)  # raises MecError without HIP/GPU
@@ -164,7 +165,7 @@ class MultimodalFusion:
         # ---- host: decode every file first
         ap = _speech._preprocessing() if present[:, 0].any() else None
         waves, wave_at, hostf, hostf_at = [], [], [], []  # compact speech rows: GPU features / host features
-        images = []  # per compact image row: (array, resized on the GPU?) (image_inference._route)
+        images = []  # per compact image row: what ImageInference.route makes of the image
         ns = ni = 0
         for b, (a, _, i) in enumerate(reqs):
             if a is not None:
@@ -183,7 +184,7 @@ class MultimodalFusion:
                 try:
                     from PIL import Image
                     with Image.open(i) as im:
-                        images.append(_route(im, self.image_inference.resize))
+                        images.append(self.image_inference.route(im))
                 except Exception as e:
                     raise ValueError(f'request {b}: cannot read image {i!r}: {e}') from e
                 ni += 1
@@ -209,7 +210,8 @@ class MultimodalFusion:
             text = (tf, tp)
         if ni:
             # one forward per model-input shape, placed in compact order; with image_resize='gpu' the images
-            # the GPU resizes are grouped by channel count and resized in one call per group
+            # the GPU resizes are grouped by channel count and resized in one call per group; with
+            # image_convert='gpu' they are converted and tested for gray there too
             image = self.image_inference.forward_routed(images)
         # ---- one routed fusion call
         plan = engine.fusion_mixed_plan(present, self.fusion_model is not None, dev)

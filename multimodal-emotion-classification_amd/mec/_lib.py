@@ -104,6 +104,11 @@ SIGNATURES = {
                                      c_vp]),
     'mec_resize_prof_enable': (c_int, [c_int]),
     'mec_resize_prof_read': (c_int, [c_dp, c_dp, ctypes.POINTER(c_int)]),
+    'mec_image_gray_ragged_u8': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, ctypes.c_size_t, c_vp, c_vp]),
+    'mec_image_canon_ragged_u8': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, ctypes.c_size_t, c_vp,
+                                          ctypes.c_size_t, c_vp]),
+    'mec_image_canon_prof_enable': (c_int, [c_int]),
+    'mec_image_canon_prof_read': (c_int, [c_dp, ctypes.POINTER(c_int), c_dp, ctypes.POINTER(c_int)]),
     'mec_gemm_f16': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp]),
     'mec_gemm_f16x3': (c_int, [c_vp, ctypes.c_longlong, c_vp, ctypes.c_longlong, ctypes.c_float, c_vp, c_vp, c_vp,
                                ctypes.c_longlong, c_vp, c_int, c_int, c_int, c_int, c_vp]),

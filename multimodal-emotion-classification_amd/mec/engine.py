@@ -523,6 +523,130 @@ def resize_ragged(arrays, device=None, channels: int = 3) -> torch.Tensor:
     return out
 
 
+def ingest_ragged(items, device=None):
+    """A list of (u8 array, fmt, palette or None) -- images in their native pixel formats, fmt one of
+    mec.image.PIX_* ([H,W] or [H,W,bpp]; a PIX_P image with its palette, u8 [768]) -> (gray, groups): gray is a
+    bool array [B], what the host's R == G == B test on the RGB-converted pixels gives; groups is
+    [(u8 [n48,48,48,1], rows), (u8 [n1,224,224,1], rows), (u8 [n3,224,224,3], rows)], device tensors holding
+    what `convert('RGB')`, the gray test, the channel selection and `resize((224, 224), Image.BILINEAR)` give on
+    the host, byte for byte, and the ascending indices into `items` of each tensor's rows: gray 48 x 48 images
+    as they are, every other gray image's one channel resized, every other image's RGB resized.
+
+    The images and the distinct palettes are packed into one pinned buffer and uploaded in one copy into a device
+    buffer with room behind them for the converted images. mec_image_gray_ragged_u8 tests them there and the B
+    flags are read back (the one synchronisation of the call: c_out and the groups depend on them);
+    mec_image_canon_ragged_u8 converts the images whose native bytes are not what their consumer reads, and one
+    mec_resize_ragged_u8 call per channel count reads untouched and converted images from the same buffer. Every
+    image must lie in mec.image.resize_on_gpu's domain (ValueError otherwise)."""
+    lib = _lib.load()
+    dev = require_gpu(device)
+    pad16 = lambda n: (int(n) + 15) // 16 * 16  # noqa: E731
+    B = len(items)
+    arrs, fmts, pals, offs, at = [], [], {}, [], 0
+    cap = 0  # the most the converted images can take
+    for i, (a, fmt, pal) in enumerate(items):
+        a = np.asarray(a)
+        if not isinstance(fmt, (int, np.integer)) or not 0 <= fmt < 5:
+            raise ValueError(f'image {i}: unknown fmt {fmt!r}')
+        bpp = _image.PIX_BPP[fmt]
+        if a.ndim == 2:
+            a = a[..., None]
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != bpp:
+            raise TypeError(f'image {i}: expected a u8 array [H,W,{bpp}] for fmt {fmt}, got {a.dtype} {a.shape}')
+        H, W = a.shape[:2]
+        if not _image.resize_on_gpu(H, W):
+            raise ValueError(f'image {i}: {H} x {W} is outside the GPU resize\'s domain')
+        if (fmt == _image.PIX_P) != (pal is not None):
+            raise ValueError(f'image {i}: a palette goes with fmt PIX_P and with no other')
+        arrs.append(a)
+        fmts.append(fmt)
+        offs.append(at)
+        at += pad16(a.size)
+        # L is read as it is unless it is a face (gathered); RGB and LA shrink to one channel at most
+        cap += pad16(H * W * (3 if fmt in (_image.PIX_RGBA, _image.PIX_P) else 1)) if (
+            fmt != _image.PIX_L or (H, W) == (48, 48)) else 0
+    pal_off = []
+    for i, (_, fmt, pal) in enumerate(items):
+        if pal is None:
+            pal_off.append(-1)
+            continue
+        pal = np.ascontiguousarray(pal, np.uint8).reshape(-1)
+        if pal.size != 768:
+            raise ValueError(f'image {i}: the palette must hold 768 bytes (256 RGB entries, zero-padded)')
+        key = pal.tobytes()
+        if key not in pals:
+            pals[key] = at
+            at += 768
+        pal_off.append(pals[key])
+    faces = torch.empty((0, 48, 48, 1), dtype=torch.uint8, device=dev)
+    if B == 0:
+        return np.zeros(0, bool), [(faces, []), (resize_ragged([], dev, 1), []), (resize_ragged([], dev, 3), [])]
+    src_total = pad16(at)
+    stage = torch.empty(src_total, dtype=torch.uint8, pin_memory=True)
+    view = stage.numpy()
+    for a, o in zip(arrs, offs):
+        view[o:o + a.size] = a.reshape(-1)
+    for key, o in pals.items():
+        view[o:o + 768] = np.frombuffer(key, np.uint8)
+    hw = np.array([a.shape[:2] for a in arrs], np.int32).reshape(B, 2)
+    npix = hw[:, 0].astype(np.int64) * hw[:, 1]
+    offs, fmts, pal_off = np.asarray(offs, np.int64), np.asarray(fmts, np.int32), np.asarray(pal_off, np.int64)
+    total = src_total + cap
+    with torch.cuda.device(dev):
+        stream = _stream(dev)
+        buf = torch.empty(total, dtype=torch.uint8, device=dev)
+        buf[:src_total].copy_(stage, non_blocking=True)
+        gray_d = torch.empty(B, dtype=torch.int32, device=dev)
+        _lib.check(lib.mec_image_gray_ragged_u8(_ptr(buf), offs.ctypes.data, hw.ctypes.data, fmts.ctypes.data,
+                                                pal_off.ctypes.data, B, src_total, _ptr(gray_d), stream),
+                   'mec_image_gray_ragged_u8')
+        gray_h = torch.empty(B, dtype=torch.int32, pin_memory=True)
+        gray_h.copy_(gray_d, non_blocking=True)
+        torch.cuda.current_stream(dev).synchronize()
+        gray = gray_h.numpy().astype(bool)
+        # ---- host: what each image's consumer reads, and where
+        face = gray & (hw[:, 0] == 48) & (hw[:, 1] == 48)
+        chan = np.where(gray, 1, 3).astype(np.int32)
+        asis = ~face & (((fmts == _image.PIX_L) & gray) | ((fmts == _image.PIX_RGB) & ~gray))
+        c_out = np.where(asis, 0, chan).astype(np.int32)
+        dst_offs, read_at, at = np.zeros(B, np.int64), offs.copy(), 0
+        for i in list(np.flatnonzero(face)) + list(np.flatnonzero(~face & ~asis)):  # the faces first, contiguous
+            dst_offs[i], read_at[i] = at, src_total + at
+            at += pad16(npix[i] * c_out[i])
+        assert at <= cap
+        if c_out.any():
+            _lib.check(lib.mec_image_canon_ragged_u8(
+                _ptr(buf), offs.ctypes.data, hw.ctypes.data, fmts.ctypes.data, pal_off.ctypes.data, c_out.ctypes.data,
+                dst_offs.ctypes.data, B, src_total, ctypes.c_void_p(buf.data_ptr() + src_total), cap, stream),
+                'mec_image_canon_ragged_u8')
+        n48 = int(face.sum())
+        groups = [(buf[src_total:src_total + n48 * 2304].view(n48, 48, 48, 1), [int(i) for i in np.flatnonzero(face)])]
+        for C in (1, 3):
+            rows = np.flatnonzero(~face & (chan == C))
+            out = torch.empty((len(rows), _image.OUT, _image.OUT, C), dtype=torch.uint8, device=dev)
+            if len(rows):
+                o, s = np.ascontiguousarray(read_at[rows]), np.ascontiguousarray(hw[rows])
+                tmp_bytes = int(s[:, 0].astype(np.int64).sum()) * _image.OUT * C
+                tmp = torch.empty(tmp_bytes, dtype=torch.uint8, device=dev)
+                _lib.check(lib.mec_resize_ragged_u8(_ptr(buf), o.ctypes.data, s.ctypes.data, len(rows), C, total,
+                                                    _ptr(tmp), tmp_bytes, _ptr(out), stream), 'mec_resize_ragged_u8')
+            groups.append((out, [int(i) for i in rows]))
+    return gray, groups
+
+
+def canon_prof(on: bool):
+    """Switch the hipEvent timing of the gray and conversion kernels on or off (process-wide)."""
+    _lib.check(_lib.load().mec_image_canon_prof_enable(int(bool(on))), 'mec_image_canon_prof_enable')
+
+
+def canon_prof_read():
+    """(gray ms, gray launches, conversion ms, conversion launches) since the last read or enable."""
+    g, c, ng, nc = ctypes.c_double(), ctypes.c_double(), ctypes.c_int(), ctypes.c_int()
+    _lib.check(_lib.load().mec_image_canon_prof_read(ctypes.byref(g), ctypes.byref(ng), ctypes.byref(c),
+                                                     ctypes.byref(nc)), 'mec_image_canon_prof_read')
+    return g.value, ng.value, c.value, nc.value
+
+
 def resize_prof(on: bool):
     """Switch the hipEvent timing of the ragged resize's two kernels on or off (process-wide)."""
     _lib.check(_lib.load().mec_resize_prof_enable(int(bool(on))), 'mec_resize_prof_enable')

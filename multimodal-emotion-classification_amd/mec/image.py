@@ -1,4 +1,5 @@
-"""The image front end's host side: which images the GPU resizes (csrc/resize.hip), and Pillow's taps.
+"""The image front end's host side: which images the GPU resizes (csrc/resize.hip) and converts
+(csrc/image_canon.hip), and Pillow's taps.
 
 Nothing here needs a GPU: the predicate and the tap builder are host functions of libmec_hip.so.
 """
@@ -17,6 +18,36 @@ def resize_on_gpu(H, W) -> bool:
     if not (0 <= H < 2 ** 31 and 0 <= W < 2 ** 31):
         return False
     return bool(_lib.load().mec_resize_on_gpu(H, W))
+
+
+# include/mec.h MEC_PIX_*: the native pixel formats the GPU ingest converts (csrc/image_canon.hip), their bytes
+# per pixel, and the Pillow modes they are
+PIX_L, PIX_LA, PIX_RGB, PIX_RGBA, PIX_P = range(5)
+PIX_BPP = (1, 2, 3, 4, 1)
+PIX_MODES = {'L': PIX_L, 'LA': PIX_LA, 'RGB': PIX_RGB, 'RGBA': PIX_RGBA, 'P': PIX_P}
+
+
+def native_pixels(image):
+    """PIL image -> (u8 pixels as decoded, fmt, palette u8 [768] or None) when the GPU ingest covers it: mode
+    L, LA, RGB or RGBA, or P with a palette whose getpalette('RGB') is not empty (zero-padded to 256 entries, as
+    convert('RGB') looks indices up), and a size inside resize_on_gpu's domain. None for every other image
+    (modes 1, I, I;16, F, CMYK, YCbCr, PA, RGBX, HSV, LAB, P without a palette, sizes outside the domain): those
+    are converted on the host. Nothing is converted or compared here."""
+    fmt = PIX_MODES.get(image.mode)
+    W, H = image.size
+    if fmt is None or not resize_on_gpu(H, W):
+        return None
+    pal = None
+    if fmt == PIX_P:
+        flat = image.getpalette('RGB')
+        if not flat or len(flat) > 768:
+            return None
+        pal = np.zeros(768, np.uint8)
+        pal[:len(flat)] = flat
+    a = np.asarray(image)
+    if a.dtype != np.uint8 or a.shape[:2] != (H, W):
+        return None
+    return a, fmt, pal
 
 
 def resize_taps(in_size: int, out_size: int = OUT, kmax: int | None = None):

@@ -1,18 +1,25 @@
-"""Time the image path from in-memory u8 arrays to probabilities with resize='host' and resize='gpu'.
+"""Time the image path from decoded images to probabilities with resize='host', resize='gpu' and
+resize='gpu' + convert='gpu'.
 
-    python3 tools/bench_image_frontend.py --out profiles/image_frontend_bench.json
+    python3 tools/bench_image_frontend.py --out profiles/image_frontend_convert_bench.json
 
-Everything is measured on the GPU host in one run. Two workloads of --batch seeded RGB u8 arrays: 'uniform'
-(every image 480 x 640) and 'ragged' (sides U[96, 1080], one image in ten gray). ImageInference.predict_arrays
-(ResNet50 f16) runs on each with the two settings alternating in one process, after a warm-up; a host clock
-runs from the list of arrays to the result dicts (so it ends behind a device synchronisation). A window is
+Everything is measured on the GPU host in one run. Four workloads of --batch seeded images: 'uniform' (RGB u8
+arrays, every image 480 x 640), 'ragged' (RGB arrays, sides U[96, 1080], one image in ten gray), 'rgba' (PIL
+images of mode RGBA, 480 x 640) and 'gray_rgb' (480 x 640 gray photos stored as RGB arrays).
+ImageInference.predict_arrays (ResNet50 f16; for the PIL images route + forward_routed, which is what predict_arrays
+runs) runs on each with the three settings alternating in one process, after a warm-up; a host clock
+runs from the list of images to the result dicts (so it ends behind a device synchronisation). A window is
 --repeats alternating calls per setting and gives each setting's median; --windows windows are taken and their
-median, minimum and maximum reported. The results of the two settings are asserted equal first.
+median, minimum and maximum reported. The results of the three settings are asserted equal first.
 
 Also reported per workload: the resize step alone on the host clock (host: PIL's resize of every image and the
 upload of the u8 224 x 224 batch; gpu: engine.resize_ragged, pack + one copy + two kernels, synchronised), and
 the two kernels' device-event times (mec_resize_prof_*) with the bytes each must move: the horizontal pass
-reads sum H W C and writes sum H 224 C, the vertical pass reads sum H 224 C and writes B 224 224 C.
+reads sum H W C and writes sum H 224 C, the vertical pass reads sum H 224 C and writes B 224 224 C. For the
+convert='gpu' setting: engine.ingest_ragged alone on the host clock (pack, one copy, the gray kernel, the flags'
+read-back, the conversion kernel, the resizes), and the gray and conversion kernels' device-event times
+(mec_image_canon_prof_*) with their bytes: the gray kernel reads the RGB / RGBA / P images, the conversion kernel
+reads the images it converts and writes H W c_out for each.
 Prints one JSON line; --out also writes it to a file.
 """
 import argparse
@@ -31,13 +38,20 @@ import torch  # noqa: E402
 from mec import engine  # noqa: E402
 
 
+KINDS = ('uniform', 'ragged', 'rgba', 'gray_rgb')
+SETTINGS = {'host': ('host', 'host'), 'gpu': ('gpu', 'host'), 'gpu_convert': ('gpu', 'gpu')}  # (resize, convert)
+
+
 def make_images(kind, B, rng):
     out = []
     for _ in range(B):
-        H, W = (480, 640) if kind == 'uniform' else (int(rng.integers(96, 1081)), int(rng.integers(96, 1081)))
-        a = rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
-        if kind == 'ragged' and rng.random() < 0.1:
+        H, W = (int(rng.integers(96, 1081)), int(rng.integers(96, 1081))) if kind == 'ragged' else (480, 640)
+        a = rng.integers(0, 256, (H, W, 4 if kind == 'rgba' else 3), dtype=np.uint8)
+        if kind == 'gray_rgb' or (kind == 'ragged' and rng.random() < 0.1):
             a = np.repeat(a[..., :1], 3, axis=2)
+        if kind == 'rgba':
+            from PIL import Image
+            a = Image.fromarray(a, 'RGBA')
         out.append(a)
     return out
 
@@ -96,6 +110,45 @@ def kernel_events(arrays, device, iters):
             'vertical': {'ms': v, 'bytes_read': tmp, 'bytes_written': out, 'GB_per_s': (tmp + out) / v / 1e6}}
 
 
+def canon_events(inf, images, device, iters):
+    """engine.ingest_ragged on what convert='gpu' hands it: the host clock of the call, and the device-event time
+    of the gray and conversion kernels per call with the bytes they move."""
+    from mec import image as mimage
+    inf.resize, inf.convert = SETTINGS['gpu_convert']
+    route = inf.route if not isinstance(images[0], np.ndarray) else inf.route_array
+    items = [tuple(route(x)) for x in images]
+    assert all(len(it) == 3 for it in items)
+    for _ in range(3):
+        gray, _ = engine.ingest_ragged(items, device)
+    host_ms = [clock(lambda: engine.ingest_ragged(items, device), device)[0] for _ in range(iters)]
+    torch.cuda.synchronize(device)
+    engine.canon_prof(True)
+    for _ in range(iters):
+        engine.ingest_ragged(items, device)
+    torch.cuda.synchronize(device)
+    g_ms, g_n, c_ms, c_n = engine.canon_prof_read()
+    engine.canon_prof(False)
+    scan = conv_r = conv_w = 0
+    for (a, fmt, _), g in zip(items, gray):
+        hw = a.shape[0] * a.shape[1]
+        if fmt not in (mimage.PIX_L, mimage.PIX_LA):
+            scan += hw * mimage.PIX_BPP[fmt]
+        face = g and a.shape[:2] == (48, 48)
+        asis = not face and ((fmt == mimage.PIX_L and g) or (fmt == mimage.PIX_RGB and not g))
+        if not asis:
+            conv_r += hw * mimage.PIX_BPP[fmt]
+            conv_w += hw * (1 if g else 3)
+    out = {'iters': iters, 'gray_images': int(gray.sum()), 'upload_bytes': sum(a.size for a, _, _ in items),
+           'ingest_ragged_host_clock_ms': {'median': statistics.median(host_ms), 'min_max': [min(host_ms), max(host_ms)]},
+           'gray_kernel': {'launches': g_n, 'bytes_read': scan},
+           'canon_kernel': {'launches': c_n, 'bytes_read': conv_r, 'bytes_written': conv_w}}
+    if g_n:
+        out['gray_kernel'].update(ms=g_ms / g_n, GB_per_s=scan / (g_ms / g_n) / 1e6)
+    if c_n:
+        out['canon_kernel'].update(ms=c_ms / c_n, GB_per_s=(conv_r + conv_w) / (c_ms / c_n) / 1e6)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('--batch', type=int, default=256)
@@ -103,6 +156,7 @@ def main():
     ap.add_argument('--repeats', type=int, default=3, help='alternating calls per setting in a window')
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--event-iters', type=int, default=20)
+    ap.add_argument('--kinds', default=','.join(KINDS), help='comma-separated workloads')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -111,32 +165,38 @@ def main():
     from inference.image_inference import ImageInference
     dev = torch.device('cuda', 0)
     B = a.batch
-    inf = ImageInference(seed=1234, device=dev, precision='f16')
+    inf = ImageInference(seed=1234, device=dev, precision='f16', resize='gpu')  # the settings are switched per call
     res = {'device': torch.cuda.get_device_name(0), 'batch': B, 'windows': a.windows, 'repeats_per_window': a.repeats,
            'warmup': a.warmup, 'pillow': PIL.__version__, 'precision': 'f16', 'backbone': 'resnet50',
            'host_threads': torch.get_num_threads()}
 
-    def predict(setting, arrays):
-        inf.resize = setting
-        return inf.predict_arrays(arrays)
+    def predict(setting, images):
+        inf.resize, inf.convert = SETTINGS[setting]
+        if isinstance(images[0], np.ndarray):
+            return inf.predict_arrays(images)
+        probs = inf.forward_routed([inf.route(im) for im in images])[1].cpu().numpy()
+        return [inf._as_dict(inf.emotions, p) for p in probs]
 
     rng = np.random.default_rng(0)
-    for kind in ('uniform', 'ragged'):
-        arrays = make_images(kind, B, rng)
-        fns = {k: (lambda k=k: predict(k, arrays)) for k in ('host', 'gpu')}
+    for kind in a.kinds.split(','):
+        images = make_images(kind, B, rng)
+        fns = {k: (lambda k=k: predict(k, images)) for k in SETTINGS}
         for _ in range(a.warmup):
             got = {k: fn() for k, fn in fns.items()}
-        assert got['host'] == got['gpu'], f'{kind}: the two settings disagree'
+        assert got['host'] == got['gpu'] == got['gpu_convert'], f'{kind}: the settings disagree'
         med = windows(fns, a.windows, a.repeats, dev)
+        arrays = [np.ascontiguousarray(np.asarray(x)[..., :3]) for x in images]  # the RGB pixels the resize step works on
         rgb = [x for x in arrays if not (x[..., 0] == x[..., 1]).all()]  # one channel count per resize call
         parts = windows({'host': lambda: host_resize(rgb, dev), 'gpu': lambda: engine.resize_ragged(rgb, dev)},
-                        a.windows, a.repeats, dev)
+                        a.windows, a.repeats, dev) if rgb else {}
         res[kind] = {'pixels_per_image_mean': float(np.mean([x.shape[0] * x.shape[1] for x in arrays])),
                      'gray_share': 1 - len(rgb) / B,
                      'arrays_to_probabilities': {k: summary(med[k], B) for k in med},
                      'gpu_over_host_speedup': statistics.median(med['host']) / statistics.median(med['gpu']),
+                     'gpu_convert_over_gpu_speedup': statistics.median(med['gpu']) / statistics.median(med['gpu_convert']),
+                     'convert_gpu': canon_events(inf, images, dev, a.event_iters),
                      'resize_only_rgb_images': {'images': len(rgb), **{k: summary(parts[k], len(rgb)) for k in parts}},
-                     'kernels_rgb_images': kernel_events(rgb, dev, a.event_iters)}
+                     'kernels_rgb_images': kernel_events(rgb, dev, a.event_iters) if rgb else None}
     print(json.dumps(res))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
