@@ -79,17 +79,6 @@ struct mec_model {
   Model* impl;
 };
 
-#define API_GUARD(body)                                  \
-  try {                                                  \
-    body                                                 \
-  } catch (const std::bad_alloc&) {                      \
-    set_error("host allocation failed");                 \
-    return -1;                                           \
-  } catch (const std::exception& e) {                    \
-    set_error(e.what());                                 \
-    return -1;                                           \
-  }
-
 static hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 // Image entry points take either backbone (ResNet50 or MobileNetV2).

@@ -3,9 +3,8 @@
 // R == G == B comparison give, for L, LA, RGB, RGBA and P. The conversion is a byte selection (L and LA replicate
 // L, RGBA drops alpha, P looks its index up in a 256-entry RGB palette), so the bytes are Pillow's. The images
 // are packed as mec_resize_ragged_u8 takes them, and the converted ones are written where that call can read
-// them through the same src pointer (csrc/resize.hip stays as it is).
+// them through the same src pointer. The host side of a call (staging, the source check) is ragged_stage.h's.
 #include <algorithm>
-#include <cstring>
 
 #include "mec.h"
 #include "mec_common.h"
@@ -131,11 +130,6 @@ std::map<int, State> g_state[2];  // [0] the gray call, [1] the canon call
 Prof& g_prof_gray = *new Prof;
 Prof& g_prof_canon = *new Prof;
 
-int fail(const char* call, int i, const std::string& what) {
-  set_error(std::string("requirement failed: ") + call + ": image " + std::to_string(i) + " " + what);
-  return -1;
-}
-
 // What both calls require of the source side, checked before anything else happens.
 int check_sources(const char* call, const int64_t* offs, const int32_t* hw, const int32_t* fmt, const int64_t* pal_off,
                   int B, size_t src_bytes, std::vector<Image>& imgs) {
@@ -144,11 +138,7 @@ int check_sources(const char* call, const int64_t* offs, const int32_t* hw, cons
     const int H = hw[2 * i], W = hw[2 * i + 1], f = fmt[i];
     if (f != MEC_PIX_L && f != MEC_PIX_LA && f != MEC_PIX_RGB && f != MEC_PIX_RGBA && f != MEC_PIX_P)
       return fail(call, i, "has the unknown fmt " + std::to_string(f));
-    if (!mec_resize_on_gpu(H, W))
-      return fail(call, i, "is " + std::to_string(H) + " x " + std::to_string(W) + ", outside 1 <= H, W <= 4096 with H <= 100 W");
-    const size_t bytes = (size_t)H * W * bpp_of(f);
-    if (offs[i] < 0 || (uint64_t)offs[i] > src_bytes || bytes > src_bytes - (size_t)offs[i])
-      return fail(call, i, "does not lie inside src_bytes");
+    MEC_TRY(check_source(call, i, H, W, bpp_of(f), offs[i], src_bytes));
     if (f == MEC_PIX_P) {
       if (pal_off[i] < 0) return fail(call, i, "is MEC_PIX_P and has no palette");
       if ((uint64_t)pal_off[i] > src_bytes || (size_t)kPalBytes > src_bytes - (size_t)pal_off[i])
@@ -163,22 +153,6 @@ int check_sources(const char* call, const int64_t* offs, const int32_t* hw, cons
 
 void add_tiles(std::vector<Tile>& tiles, int img, long long npix) {
   for (long long p = 0; p < npix; p += kTilePix) tiles.push_back(Tile{img, (int)p, (int)std::min<long long>(kTilePix, npix - p)});
-}
-
-// Uploads imgs | tiles from the entry's staging buffer; the caller holds g_mu and records st.done afterwards.
-int upload(State& st, const std::vector<Image>& imgs, const std::vector<Tile>& tiles, hipStream_t s, const Image** d_imgs,
-           const Tile** d_tiles) {
-  const size_t tile_at = pad16(imgs.size() * sizeof(Image));
-  const size_t total = tile_at + std::max<size_t>(tiles.size(), 1) * sizeof(Tile);
-  MEC_TRY(ensure(st, total));
-  char* h = static_cast<char*>(st.host);
-  std::memcpy(h, imgs.data(), imgs.size() * sizeof(Image));
-  std::memcpy(h + tile_at, tiles.data(), tiles.size() * sizeof(Tile));
-  MEC_HIP(hipMemcpyAsync(st.dev, st.host, total, hipMemcpyHostToDevice, s));
-  st.pending = true;  // from here on the buffers are in use until `done`
-  *d_imgs = reinterpret_cast<const Image*>(st.dev);
-  *d_tiles = reinterpret_cast<const Tile*>(static_cast<const char*>(st.dev) + tile_at);
-  return 0;
 }
 
 int gray_ragged(const uint8_t* src, const int64_t* offs, const int32_t* hw, const int32_t* fmt, const int64_t* pal_off,
@@ -198,11 +172,10 @@ int gray_ragged(const uint8_t* src, const int64_t* offs, const int32_t* hw, cons
   int dev = 0;
   MEC_HIP(hipGetDevice(&dev));
   std::lock_guard<std::mutex> lk(g_mu);
-  State& st = g_state[0][dev];
-  const Image* d_imgs = nullptr;
-  const Tile* d_tiles = nullptr;
-  MEC_TRY(upload(st, imgs, tiles, s, &d_imgs, &d_tiles));
-  auto launch = [&]() -> int {
+  const Section sec[] = {section(imgs), section(tiles)};
+  return staged_call(g_state[0][dev], sec, s, [&](const void* const* d) -> int {
+    const Image* d_imgs = static_cast<const Image*>(d[0]);
+    const Tile* d_tiles = static_cast<const Tile*>(d[1]);
     MEC_HIP(hipMemsetAsync(gray, 0, (size_t)B * sizeof(int32_t), s));  // the per-image "colour found" words
     if (!tiles.empty()) {
       MEC_TRY(g_prof_gray.begin(TAG_CANON_GRAY, s));
@@ -213,10 +186,7 @@ int gray_ragged(const uint8_t* src, const int64_t* offs, const int32_t* hw, cons
     hipLaunchKernelGGL(flags_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, gray, B);
     MEC_LAUNCH_CHECK();
     return 0;
-  };
-  const int rc = launch();
-  MEC_HIP(hipEventRecord(st.done, s));
-  return rc;
+  });
 }
 
 int canon_ragged(const uint8_t* src, const int64_t* offs, const int32_t* hw, const int32_t* fmt, const int64_t* pal_off,
@@ -267,20 +237,15 @@ int canon_ragged(const uint8_t* src, const int64_t* offs, const int32_t* hw, con
   int dev = 0;
   MEC_HIP(hipGetDevice(&dev));
   std::lock_guard<std::mutex> lk(g_mu);
-  State& st = g_state[1][dev];
-  const Image* d_imgs = nullptr;
-  const Tile* d_tiles = nullptr;
-  MEC_TRY(upload(st, imgs, tiles, s, &d_imgs, &d_tiles));
-  auto launch = [&]() -> int {
+  const Section sec[] = {section(imgs), section(tiles)};
+  return staged_call(g_state[1][dev], sec, s, [&](const void* const* d) -> int {
     MEC_TRY(g_prof_canon.begin(TAG_CANON_PIX, s));
-    hipLaunchKernelGGL(canon_kernel, dim3((unsigned)tiles.size()), dim3(256), 0, s, src, d_imgs, d_tiles, dst);
+    hipLaunchKernelGGL(canon_kernel, dim3((unsigned)tiles.size()), dim3(256), 0, s, src, static_cast<const Image*>(d[0]),
+                       static_cast<const Tile*>(d[1]), dst);
     MEC_LAUNCH_CHECK();
     MEC_TRY(g_prof_canon.end(TAG_CANON_PIX, s));
     return 0;
-  };
-  const int rc = launch();
-  MEC_HIP(hipEventRecord(st.done, s));
-  return rc;
+  });
 }
 
 }  // namespace ic
@@ -292,24 +257,18 @@ extern "C" {
 
 int mec_image_gray_ragged_u8(const uint8_t* src, const int64_t* offs, const int32_t* hw, const int32_t* fmt,
                              const int64_t* pal_off, int B, size_t src_bytes, int32_t* gray, void* stream) {
-  try {
+  API_GUARD({
     return ic::gray_ragged(src, offs, hw, fmt, pal_off, B, src_bytes, gray, reinterpret_cast<hipStream_t>(stream));
-  } catch (const std::exception& e) {
-    set_error(std::string("mec_image_gray_ragged_u8: ") + e.what());
-    return -1;
-  }
+  })
 }
 
 int mec_image_canon_ragged_u8(const uint8_t* src, const int64_t* offs, const int32_t* hw, const int32_t* fmt,
                               const int64_t* pal_off, const int32_t* c_out, const int64_t* dst_offs, int B,
                               size_t src_bytes, uint8_t* dst, size_t dst_bytes, void* stream) {
-  try {
+  API_GUARD({
     return ic::canon_ragged(src, offs, hw, fmt, pal_off, c_out, dst_offs, B, src_bytes, dst, dst_bytes,
                             reinterpret_cast<hipStream_t>(stream));
-  } catch (const std::exception& e) {
-    set_error(std::string("mec_image_canon_ragged_u8: ") + e.what());
-    return -1;
-  }
+  })
 }
 
 int mec_image_canon_prof_enable(int on) {

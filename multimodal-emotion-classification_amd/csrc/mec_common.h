@@ -6,6 +6,8 @@
 #include <cstdint>
 #include <map>
 #include <mutex>
+#include <new>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -43,6 +45,18 @@ void set_error(const std::string& msg);
   } while (0)
 
 #define MEC_LAUNCH_CHECK() MEC_HIP(hipGetLastError())
+
+// The body of an extern "C" entry point: no exception crosses the C ABI, it becomes -1 and the error text.
+#define API_GUARD(body)                                  \
+  try {                                                  \
+    body                                                 \
+  } catch (const std::bad_alloc&) {                      \
+    ::mec::set_error("host allocation failed");          \
+    return -1;                                           \
+  } catch (const std::exception& e) {                    \
+    ::mec::set_error(e.what());                          \
+    return -1;                                           \
+  }
 
 // Kernel tags for the hipEvent timing hook (mec_prof_enable); see DESIGN.md §Measurement.
 enum KernelTag : int {

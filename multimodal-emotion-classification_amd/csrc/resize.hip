@@ -6,7 +6,6 @@
 // (resnet.hip resize_u8) is a kernel of its own and stays as it is.
 #include <algorithm>
 #include <cmath>
-#include <cstring>
 
 #include "mec.h"
 #include "mec_common.h"
@@ -222,16 +221,7 @@ int resize_ragged(const uint8_t* src, const int64_t* offs, const int32_t* hw, in
   size_t need = 0;
   for (int i = 0; i < B; ++i) {
     const int H = hw[2 * i], W = hw[2 * i + 1];
-    if (!on_gpu(H, W)) {
-      set_error("requirement failed: mec_resize_ragged_u8: image " + std::to_string(i) + " is " + std::to_string(H) +
-                " x " + std::to_string(W) + ", outside 1 <= H, W <= 4096 with H <= 100 W");
-      return -1;
-    }
-    const size_t bytes = (size_t)H * W * C;
-    if (offs[i] < 0 || (uint64_t)offs[i] > src_bytes || bytes > src_bytes - (size_t)offs[i]) {
-      set_error("requirement failed: mec_resize_ragged_u8: image " + std::to_string(i) + " does not lie inside src_bytes");
-      return -1;
-    }
+    MEC_TRY(check_source("mec_resize_ragged_u8", i, H, W, C, offs[i], src_bytes));
     Image& im = imgs[i];
     im.src_off = offs[i];
     im.tmp_off = (long long)need;
@@ -255,23 +245,11 @@ int resize_ragged(const uint8_t* src, const int64_t* offs, const int32_t* hw, in
   int dev = 0;
   MEC_HIP(hipGetDevice(&dev));
   std::lock_guard<std::mutex> lk(g_mu);
-  State& st = g_state[dev];
-  const size_t tile_at = pad16(imgs.size() * sizeof(Image));
-  const size_t taps_at = tile_at + pad16(tiles.size() * sizeof(Tile));
-  const size_t total = taps_at + taps.size() * sizeof(int);
-  MEC_TRY(ensure(st, total));
-  char* h = static_cast<char*>(st.host);
-  std::memcpy(h, imgs.data(), imgs.size() * sizeof(Image));
-  std::memcpy(h + tile_at, tiles.data(), tiles.size() * sizeof(Tile));
-  std::memcpy(h + taps_at, taps.data(), taps.size() * sizeof(int));
-  MEC_HIP(hipMemcpyAsync(st.dev, st.host, total, hipMemcpyHostToDevice, s));
-  st.pending = true;  // from here on the buffers are in use until `done`
-  const char* d = static_cast<const char*>(st.dev);
-  const Image* d_imgs = reinterpret_cast<const Image*>(d);
-  const Tile* d_tiles = reinterpret_cast<const Tile*>(d + tile_at);
-  const int* d_taps = reinterpret_cast<const int*>(d + taps_at);
-  int rc = 0;
-  auto launch = [&]() -> int {
+  const Section sec[] = {section(imgs), section(tiles), section(taps)};
+  return staged_call(g_state[dev], sec, s, [&](const void* const* d) -> int {
+    const Image* d_imgs = static_cast<const Image*>(d[0]);
+    const Tile* d_tiles = static_cast<const Tile*>(d[1]);
+    const int* d_taps = static_cast<const int*>(d[2]);
     MEC_TRY(g_prof_h.begin(TAG_RESIZE_H, s));
     if (C == 1)
       hipLaunchKernelGGL(horizontal_kernel<1>, dim3((unsigned)tiles.size()), dim3(256), 0, s, src, d_imgs, d_tiles, d_taps, tmp);
@@ -288,10 +266,7 @@ int resize_ragged(const uint8_t* src, const int64_t* offs, const int32_t* hw, in
     MEC_LAUNCH_CHECK();
     MEC_TRY(g_prof_v.end(TAG_RESIZE_V, s));
     return 0;
-  };
-  rc = launch();
-  MEC_HIP(hipEventRecord(st.done, s));
-  return rc;
+  });
 }
 
 }  // namespace rr
@@ -304,26 +279,20 @@ extern "C" {
 int mec_resize_on_gpu(int H, int W) { return rr::on_gpu(H, W) ? 1 : 0; }
 
 int mec_resize_taps(int in_size, int out_size, int32_t* xmin, int32_t* n, int32_t* k, int kmax) {
-  try {
+  API_GUARD({
     MEC_REQUIRE(in_size >= 1 && out_size >= 1, "mec_resize_taps: in_size and out_size must be at least 1");
     MEC_REQUIRE(xmin && n && k, "mec_resize_taps: xmin, n or k is null");
     MEC_REQUIRE(kmax >= rr::ksize_of(in_size, out_size), "mec_resize_taps: kmax is less than 2 * ceil(max(in / out, 1)) + 1");
     rr::build_taps(in_size, out_size, xmin, n, k, kmax);
     return 0;
-  } catch (const std::exception& e) {
-    set_error(std::string("mec_resize_taps: ") + e.what());
-    return -1;
-  }
+  })
 }
 
 int mec_resize_ragged_u8(const uint8_t* src, const int64_t* offs, const int32_t* hw, int B, int C, size_t src_bytes,
                          uint8_t* tmp, size_t tmp_bytes, uint8_t* out, void* stream) {
-  try {
+  API_GUARD({
     return rr::resize_ragged(src, offs, hw, B, C, src_bytes, tmp, tmp_bytes, out, reinterpret_cast<hipStream_t>(stream));
-  } catch (const std::exception& e) {
-    set_error(std::string("mec_resize_ragged_u8: ") + e.what());
-    return -1;
-  }
+  })
 }
 
 int mec_resize_prof_enable(int on) {

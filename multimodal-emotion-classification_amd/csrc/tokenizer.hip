@@ -454,21 +454,18 @@ int create(const mec_tok_desc* d, const tok::HostTable& t, const tok::CpTable* c
 extern "C" {
 
 int mec_tok_create(const mec_tok_desc* d, int device, mec_tokenizer** out) {
-  try {
+  API_GUARD({
     if (!out) { set_error("mec_tok_create: out is null"); return -1; }
     *out = nullptr;
     tok::HostTable t;
     std::string err;
     if (tok::build(d, &t, &err) != 0) { set_error(err); return -1; }
     return create(d, t, nullptr, device, out);
-  } catch (const std::exception& e) {
-    set_error(std::string("mec_tok_create: ") + e.what());
-    return -1;
-  }
+  })
 }
 
 int mec_tok_create_utf8(const mec_tok_desc* d, const mec_tok_cpmap* m, int device, mec_tokenizer** out) {
-  try {
+  API_GUARD({
     if (!out) { set_error("mec_tok_create_utf8: out is null"); return -1; }
     *out = nullptr;
     tok::HostTable t;
@@ -476,10 +473,7 @@ int mec_tok_create_utf8(const mec_tok_desc* d, const mec_tok_cpmap* m, int devic
     std::string err;
     if (tok::build(d, &t, &err, true) != 0 || tok::build_cpmap(m, d->lower, &cp, &err) != 0) { set_error(err); return -1; }
     return create(d, t, &cp, device, out);
-  } catch (const std::exception& e) {
-    set_error(std::string("mec_tok_create_utf8: ") + e.what());
-    return -1;
-  }
+  })
 }
 
 int mec_tok_encode(mec_tokenizer* t, const uint8_t* text, const int64_t* text_off, int B, int L, int32_t* ids,

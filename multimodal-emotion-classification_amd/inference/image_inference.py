@@ -32,7 +32,7 @@ import numpy as np
 from config import Config
 from mec import checkpoints, engine
 from mec._lib import MecError
-from mec.image import PIX_L, PIX_RGB, native_pixels, resize_on_gpu
+from mec.image import MODEL_SHAPES, PIX_L, PIX_RGB, native_pixels, resize_on_gpu
 
 
 def _route(image, resize: str = 'host'):
@@ -52,11 +52,6 @@ def _route(image, resize: str = 'host'):
     return np.ascontiguousarray(r[..., :1] if gray else r), False
 
 
-def _to_model_input(image) -> np.ndarray:
-    """PIL image -> u8 array [H,W,C] in one of the shapes the HIP path takes."""
-    return _route(image, 'host')[0]
-
-
 def _as_image(arr):
     """u8 array [H,W] / [H,W,1] (gray) or [H,W,3] (RGB) -> PIL image."""
     from PIL import Image
@@ -66,6 +61,19 @@ def _as_image(arr):
     if a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] != 3):
         raise ValueError(f'image array: shape {a.shape} is not [H,W], [H,W,1] or [H,W,3]')
     return Image.fromarray(np.ascontiguousarray(a), 'L' if a.ndim == 2 else 'RGB')
+
+
+def plan_batches(made):
+    """made: per item of a `forward_routed` list, (its model-input shape, whether the device makes it) ->
+    {shape: (rows, device slots, host slots)} for the three shapes: the shape's rows in ascending order, which is
+    its forward's batch, and where in that batch the device-made and the host-made rows stand, each ascending (the
+    order in which either part holds its rows)."""
+    plan = {shape: ([], [], []) for shape in MODEL_SHAPES}
+    for row, (shape, on_device) in enumerate(made):
+        rows, dev_at, host_at = plan[tuple(shape)]
+        (dev_at if on_device else host_at).append(len(rows))
+        rows.append(row)
+    return plan
 
 
 class Native(tuple):
@@ -116,36 +124,58 @@ class ImageInference:
         feat, logits, probs = self.model.checked('forward_u8', x)
         return feat.cpu().numpy()[0], probs.cpu().numpy()[0]
 
+    def _device_parts(self, rows, pixels, ingest):
+        """The device-made rows of a `forward_routed` list -> {model-input shape: (u8 batch on the device, its
+        rows, ascending)}. `pixels` are engine.ingest_ragged items. ingest True (the list holds a `Native`): one
+        engine.ingest_ragged call; False (L or RGB pixels only): one engine.resize_ragged call per channel count."""
+        if ingest:
+            _, groups = engine.ingest_ragged(pixels, self.device)
+            return {shape: (x, [rows[j] for j in local]) for shape, (x, local) in zip(MODEL_SHAPES, groups)}
+        parts = {}
+        for C in (1, 3):
+            local = [j for j, px in enumerate(pixels) if px[0].shape[2] == C]
+            if local:
+                parts[(224, 224, C)] = (engine.resize_ragged([pixels[j][0] for j in local], self.device),
+                                        [rows[j] for j in local])
+        return parts
+
     def forward_routed(self, items):
-        """items: a list of `_route` results (`route` results: with `Native` items among them the list takes
-        `_forward_ingested`, which builds the same batches) -> (feat [n,512], probs [n,7]) device tensors in the list's order.
+        """items: a list of `route` results -> (feat [n,512], probs [n,7]) device tensors in the list's order.
         One forward per model-input shape, (48,48,1) / (224,224,1) / (224,224,3), as a batch of PIL-resized
-        images is grouped: a shape's ragged images are resized in one call (ImageEncoder.forward_ragged when
-        the group holds nothing else) and stand in the group's batch where PIL's results would, so both
-        settings of `resize` run the same forwards on the same bytes."""
+        images is grouped: the rows made on the device (`_device_parts`: `Native` items and `_route` results
+        still to be resized) stand in their shape's batch where the host's results would, in ascending row order
+        (`plan_batches`), so every setting of `resize` and `convert` runs the same forwards on the same bytes."""
         import torch
-        if any(isinstance(it, Native) for it in items):
-            return self._forward_ingested(items)
         dev = self.device
         at = lambda rows: torch.tensor(rows, dtype=torch.int64, device=dev)  # noqa: E731
-        groups = {}  # model-input shape -> [rows, host arrays, their slots, ragged arrays, their slots]
-        for row, (arr, ragged) in enumerate(items):
-            g = groups.setdefault((224, 224, arr.shape[2]) if ragged else arr.shape, [[], [], [], [], []])
-            (g[3] if ragged else g[1]).append(arr)
-            (g[4] if ragged else g[2]).append(len(g[0]))
-            g[0].append(row)
+        host, drows, pixels = {}, [], []  # row -> host-made array; the device-made rows and their pixels
+        for row, it in enumerate(items):
+            if isinstance(it, Native):
+                pixels.append(tuple(it))
+            elif it[1]:
+                pixels.append((it[0], PIX_L if it[0].shape[2] == 1 else PIX_RGB, None))
+            else:
+                host[row] = it[0]
+                continue
+            drows.append(row)
+        parts = self._device_parts(drows, pixels, any(isinstance(it, Native) for it in items))
+        made = {row: (a.shape, False) for row, a in host.items()}
+        made.update((row, (shape, True)) for shape, (_, prows) in parts.items() for row in prows)
         feat = torch.empty((len(items), 512), dtype=torch.float32, device=dev)
         probs = torch.empty((len(items), 7), dtype=torch.float32, device=dev)
-        for shape, (rows, host, host_at, ragged, ragged_at) in groups.items():
-            if not ragged:
-                f, _, p = self.model.checked('forward_u8', engine.to_device(np.stack(host), dev))
-            elif not host:
-                f, _, p = self.model.checked('forward_ragged', ragged)
-            else:
-                x = torch.empty((len(rows),) + shape, dtype=torch.uint8, device=dev)
-                x.index_copy_(0, at(ragged_at), engine.resize_ragged(ragged, dev))
-                x.index_copy_(0, at(host_at), engine.to_device(np.stack(host), dev))
-                f, _, p = self.model.checked('forward_u8', x)
+        for shape, (rows, dev_at, host_at) in plan_batches([made[row] for row in range(len(items))]).items():
+            if not rows:
+                continue
+            x = parts[shape][0] if dev_at else None
+            if host_at:
+                h = engine.to_device(np.stack([host[rows[k]] for k in host_at]), dev)
+                if dev_at:  # a part that is the whole batch is used as it is
+                    x, part = torch.empty((len(rows),) + shape, dtype=torch.uint8, device=dev), x
+                    x.index_copy_(0, at(dev_at), part)
+                    x.index_copy_(0, at(host_at), h)
+                else:
+                    x = h
+            f, _, p = self.model.checked('forward_u8', x)
             feat.index_copy_(0, at(rows), f)
             probs.index_copy_(0, at(rows), p)
         return feat, probs
@@ -173,47 +203,6 @@ class ImageInference:
         if a.ndim in (2, 3) and (a.ndim == 2 or a.shape[2] == 3) and resize_on_gpu(a.shape[0], a.shape[1]):
             return Native((a, PIX_L if a.ndim == 2 else PIX_RGB, None))
         return _route(_as_image(a), self.resize)  # raises for a shape that is no image's
-
-    def _forward_ingested(self, items):
-        """`forward_routed` for a list that holds `Native` items: they, and the `_route` results still to be
-        resized (L or RGB pixels by then), go through one engine.ingest_ragged call; its three batches and the
-        host-made arrays are merged per model-input shape in ascending row order, so every forward sees the batch
-        convert='host' builds."""
-        import torch
-        dev = self.device
-        at = lambda rows: torch.tensor(rows, dtype=torch.int64, device=dev)  # noqa: E731
-        shapes = ((48, 48, 1), (224, 224, 1), (224, 224, 3))
-        host = {s: ([], []) for s in shapes}  # model-input shape -> rows, host arrays
-        native, native_rows = [], []
-        for row, it in enumerate(items):
-            if isinstance(it, Native):
-                native.append(tuple(it))
-            elif it[1]:
-                native.append((it[0], PIX_L if it[0].shape[2] == 1 else PIX_RGB, None))
-            else:
-                host[it[0].shape][0].append(row)
-                host[it[0].shape][1].append(it[0])
-                continue
-            native_rows.append(row)
-        _, groups = engine.ingest_ragged(native, dev)
-        feat = torch.empty((len(items), 512), dtype=torch.float32, device=dev)
-        probs = torch.empty((len(items), 7), dtype=torch.float32, device=dev)
-        for shape, (x, local) in zip(shapes, groups):
-            grows, (hrows, harrs) = [native_rows[j] for j in local], host[shape]
-            rows = sorted(grows + hrows)
-            if not rows:
-                continue
-            if hrows:
-                slot = {r: k for k, r in enumerate(rows)}
-                merged = torch.empty((len(rows),) + shape, dtype=torch.uint8, device=dev)
-                if grows:
-                    merged.index_copy_(0, at([slot[r] for r in grows]), x)
-                merged.index_copy_(0, at([slot[r] for r in hrows]), engine.to_device(np.stack(harrs), dev))
-                x = merged
-            f, _, p = self.model.checked('forward_u8', x)
-            feat.index_copy_(0, at(rows), f)
-            probs.index_copy_(0, at(rows), p)
-        return feat, probs
 
     def _forward_image(self, image):
         item = self.route(image)

@@ -487,38 +487,36 @@ def resize_ragged(arrays, device=None, channels: int = 3) -> torch.Tensor:
     dev = require_gpu(device)
     arrs = []
     for i, a in enumerate(arrays):
-        a = np.asarray(a)
-        if a.ndim == 2:
-            a = a[..., None]
-        if a.dtype != np.uint8 or a.ndim != 3:
-            raise TypeError(f'image {i}: expected a u8 array [H,W,C], got {a.dtype} {a.shape}')
-        arrs.append(a)
+        arrs.append(_image.check_image(i, a, arrs[0].shape[2] if arrs else None))
     C = arrs[0].shape[2] if arrs else int(channels)
     if C not in (1, 3):
         raise ValueError(f'C must be 1 or 3, got {C}')
-    for i, a in enumerate(arrs):
-        if a.shape[2] != C:
-            raise ValueError(f'image {i}: {a.shape[2]} channels in a batch of C = {C}')
-        if not _image.resize_on_gpu(a.shape[0], a.shape[1]):
-            raise ValueError(f'image {i}: {a.shape[0]} x {a.shape[1]} is outside the GPU resize\'s domain')
-    B = len(arrs)
-    out = torch.empty((B, _image.OUT, _image.OUT, C), dtype=torch.uint8, device=dev)
-    if B == 0:
-        return out
-    hw = np.array([a.shape[:2] for a in arrs], np.int32).reshape(B, 2)
-    size = hw[:, 0].astype(np.int64) * hw[:, 1] * C
-    offs = np.zeros(B, np.int64)
-    offs[1:] = np.cumsum((size[:-1] + 15) // 16 * 16)  # every image starts on a 16-byte boundary
-    total = int(offs[-1] + size[-1])
+    hw = np.array([a.shape[:2] for a in arrs], np.int32).reshape(-1, 2)
+    offs, _, total = _image.pack_layout([a.size for a in arrs])
+    with torch.cuda.device(dev):
+        src = _pinned(total, zip(offs, arrs)).to(dev, non_blocking=True) if arrs else None
+        return _resize_on_device(lib, src, offs, hw, C, total, dev)
+
+
+def _pinned(total, pieces) -> torch.Tensor:
+    """A pinned u8 staging tensor of `total` bytes holding each (offset, u8 array) of `pieces`."""
     stage = torch.empty(total, dtype=torch.uint8, pin_memory=True)
     view = stage.numpy()
-    for a, o, n in zip(arrs, offs, size):
-        view[o:o + n] = a.reshape(-1)
-    tmp_bytes = int(hw[:, 0].astype(np.int64).sum()) * _image.OUT * C
-    with torch.cuda.device(dev):
-        src = stage.to(dev, non_blocking=True)
+    for o, a in pieces:
+        view[o:o + a.size] = a.reshape(-1)
+    return stage
+
+
+def _resize_on_device(lib, src, offs, hw, C, src_bytes, dev) -> torch.Tensor:
+    """mec_resize_ragged_u8 on the images at `offs` (int64 [B]) of the device buffer `src`, of extents `hw`
+    (int32 [B,2]) and C channels -> u8 [B,224,224,C]. Allocates the result and the horizontal pass'
+    intermediate, sum(H) * 224 * C bytes; an empty batch makes no call. `dev` is the current device."""
+    B = len(offs)
+    out = torch.empty((B, _image.OUT, _image.OUT, C), dtype=torch.uint8, device=dev)
+    if B:
+        tmp_bytes = int(hw[:, 0].astype(np.int64).sum()) * _image.OUT * C
         tmp = torch.empty(tmp_bytes, dtype=torch.uint8, device=dev)
-        _lib.check(lib.mec_resize_ragged_u8(_ptr(src), offs.ctypes.data, hw.ctypes.data, B, C, total, _ptr(tmp),
+        _lib.check(lib.mec_resize_ragged_u8(_ptr(src), offs.ctypes.data, hw.ctypes.data, B, C, src_bytes, _ptr(tmp),
                                             tmp_bytes, _ptr(out), _stream(dev)), 'mec_resize_ragged_u8')
     return out
 
@@ -540,58 +538,26 @@ def ingest_ragged(items, device=None):
     image must lie in mec.image.resize_on_gpu's domain (ValueError otherwise)."""
     lib = _lib.load()
     dev = require_gpu(device)
-    pad16 = lambda n: (int(n) + 15) // 16 * 16  # noqa: E731
     B = len(items)
-    arrs, fmts, pals, offs, at = [], [], {}, [], 0
-    cap = 0  # the most the converted images can take
-    for i, (a, fmt, pal) in enumerate(items):
-        a = np.asarray(a)
-        if not isinstance(fmt, (int, np.integer)) or not 0 <= fmt < 5:
-            raise ValueError(f'image {i}: unknown fmt {fmt!r}')
-        bpp = _image.PIX_BPP[fmt]
-        if a.ndim == 2:
-            a = a[..., None]
-        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != bpp:
-            raise TypeError(f'image {i}: expected a u8 array [H,W,{bpp}] for fmt {fmt}, got {a.dtype} {a.shape}')
-        H, W = a.shape[:2]
-        if not _image.resize_on_gpu(H, W):
-            raise ValueError(f'image {i}: {H} x {W} is outside the GPU resize\'s domain')
-        if (fmt == _image.PIX_P) != (pal is not None):
-            raise ValueError(f'image {i}: a palette goes with fmt PIX_P and with no other')
-        arrs.append(a)
-        fmts.append(fmt)
-        offs.append(at)
-        at += pad16(a.size)
-        # L is read as it is unless it is a face (gathered); RGB and LA shrink to one channel at most
-        cap += pad16(H * W * (3 if fmt in (_image.PIX_RGBA, _image.PIX_P) else 1)) if (
-            fmt != _image.PIX_L or (H, W) == (48, 48)) else 0
-    pal_off = []
-    for i, (_, fmt, pal) in enumerate(items):
-        if pal is None:
-            pal_off.append(-1)
-            continue
-        pal = np.ascontiguousarray(pal, np.uint8).reshape(-1)
-        if pal.size != 768:
-            raise ValueError(f'image {i}: the palette must hold 768 bytes (256 RGB entries, zero-padded)')
-        key = pal.tobytes()
-        if key not in pals:
-            pals[key] = at
-            at += 768
-        pal_off.append(pals[key])
-    faces = torch.empty((0, 48, 48, 1), dtype=torch.uint8, device=dev)
+    arrs = [_image.check_image(i, a, fmt=fmt, pal=pal) for i, (a, fmt, pal) in enumerate(items)]
+    pals = []
+    for i, (_, _, pal) in enumerate(items):
+        if pal is not None:
+            pal = np.ascontiguousarray(pal, np.uint8).reshape(-1)
+            if pal.size != _image.PAL_BYTES:
+                raise ValueError(f'image {i}: the palette must hold 768 bytes (256 RGB entries, zero-padded)')
+            pal = pal.tobytes()
+        pals.append(pal)
     if B == 0:
-        return np.zeros(0, bool), [(faces, []), (resize_ragged([], dev, 1), []), (resize_ragged([], dev, 3), [])]
-    src_total = pad16(at)
-    stage = torch.empty(src_total, dtype=torch.uint8, pin_memory=True)
-    view = stage.numpy()
-    for a, o in zip(arrs, offs):
-        view[o:o + a.size] = a.reshape(-1)
-    for key, o in pals.items():
-        view[o:o + 768] = np.frombuffer(key, np.uint8)
+        return np.zeros(0, bool), [(torch.empty((0,) + s, dtype=torch.uint8, device=dev), []) for s in _image.MODEL_SHAPES]
+    fmts = np.array([fmt for _, fmt, _ in items], np.int32)
     hw = np.array([a.shape[:2] for a in arrs], np.int32).reshape(B, 2)
-    npix = hw[:, 0].astype(np.int64) * hw[:, 1]
-    offs, fmts, pal_off = np.asarray(offs, np.int64), np.asarray(fmts, np.int32), np.asarray(pal_off, np.int64)
+    offs, pal_at, end = _image.pack_layout([a.size for a in arrs], [p for p in pals if p is not None])
+    pal_off = np.array([-1 if p is None else pal_at[p] for p in pals], np.int64)
+    src_total = _image.pad16(end)
+    cap = sum(_image.canon_room(f, H, W) for f, (H, W) in zip(fmts, hw.tolist()))  # the most the converted images take
     total = src_total + cap
+    stage = _pinned(src_total, list(zip(offs, arrs)) + [(o, np.frombuffer(p, np.uint8)) for p, o in pal_at.items()])
     with torch.cuda.device(dev):
         stream = _stream(dev)
         buf = torch.empty(total, dtype=torch.uint8, device=dev)
@@ -604,16 +570,7 @@ def ingest_ragged(items, device=None):
         gray_h.copy_(gray_d, non_blocking=True)
         torch.cuda.current_stream(dev).synchronize()
         gray = gray_h.numpy().astype(bool)
-        # ---- host: what each image's consumer reads, and where
-        face = gray & (hw[:, 0] == 48) & (hw[:, 1] == 48)
-        chan = np.where(gray, 1, 3).astype(np.int32)
-        asis = ~face & (((fmts == _image.PIX_L) & gray) | ((fmts == _image.PIX_RGB) & ~gray))
-        c_out = np.where(asis, 0, chan).astype(np.int32)
-        dst_offs, read_at, at = np.zeros(B, np.int64), offs.copy(), 0
-        for i in list(np.flatnonzero(face)) + list(np.flatnonzero(~face & ~asis)):  # the faces first, contiguous
-            dst_offs[i], read_at[i] = at, src_total + at
-            at += pad16(npix[i] * c_out[i])
-        assert at <= cap
+        face, chan, c_out, dst_offs, read_at = _image.canon_plan(gray, hw, fmts, offs, src_total)
         if c_out.any():
             _lib.check(lib.mec_image_canon_ragged_u8(
                 _ptr(buf), offs.ctypes.data, hw.ctypes.data, fmts.ctypes.data, pal_off.ctypes.data, c_out.ctypes.data,
@@ -623,13 +580,8 @@ def ingest_ragged(items, device=None):
         groups = [(buf[src_total:src_total + n48 * 2304].view(n48, 48, 48, 1), [int(i) for i in np.flatnonzero(face)])]
         for C in (1, 3):
             rows = np.flatnonzero(~face & (chan == C))
-            out = torch.empty((len(rows), _image.OUT, _image.OUT, C), dtype=torch.uint8, device=dev)
-            if len(rows):
-                o, s = np.ascontiguousarray(read_at[rows]), np.ascontiguousarray(hw[rows])
-                tmp_bytes = int(s[:, 0].astype(np.int64).sum()) * _image.OUT * C
-                tmp = torch.empty(tmp_bytes, dtype=torch.uint8, device=dev)
-                _lib.check(lib.mec_resize_ragged_u8(_ptr(buf), o.ctypes.data, s.ctypes.data, len(rows), C, total,
-                                                    _ptr(tmp), tmp_bytes, _ptr(out), stream), 'mec_resize_ragged_u8')
+            out = _resize_on_device(lib, buf, np.ascontiguousarray(read_at[rows]), np.ascontiguousarray(hw[rows]), C,
+                                    total, dev)
             groups.append((out, [int(i) for i in rows]))
     return gray, groups
 

@@ -315,6 +315,44 @@ def test_image_inference_convert_gpu_equals_host(dev, precision, monkeypatch):
         inf.extract_features_arrays([np.zeros((5, 5, 2), np.uint8)])
 
 
+def test_forward_routed_merges_every_shape(dev):
+    """Nine small images such that every model-input shape's batch interleaves host-made and device-made rows,
+    under both sources of the device-made rows (engine.resize_ragged per channel count, engine.ingest_ragged):
+    (48,48,1) rows 1, 4; (224,224,1) rows 2, 6, 8; (224,224,3) rows 0, 3, 5, 7. The three settings' results are
+    equal bit for bit."""
+    from PIL import Image
+    from inference.image_inference import ImageInference, Native
+    f = cr.formula
+    images = [Image.fromarray(f(100, 120, 3), 'RGB'),  # an RGB photo: the device's
+              Image.fromarray(f(48, 48, 1, 5)[..., 0] > 127),  # a mode-1 face: converted on the host, its own kernel
+              Image.fromarray(f(60, 80, 1, 4)[..., 0], 'L'),  # an L photo: the device's
+              Image.fromarray(f(301, 3, 3), 'RGB'),  # the strip, outside the domain: the host's
+              Image.fromarray(f(48, 48, 1, 6)[..., 0], 'L'),  # an L face: the host's, ingested with convert='gpu'
+              Image.fromarray(f(80, 60, 4, 1), 'CMYK'),  # converted on the host, resized on the device
+              Image.fromarray(f(301, 3, 1, 2)[..., 0], 'L'),  # a gray strip: the host's
+              Image.fromarray(f(75, 55, 4, 2), 'RGBA'),  # colour RGBA: the device's
+              Image.fromarray(np.repeat(f(90, 70, 1, 7), 3, 2), 'RGB')]  # a gray-valued RGB photo: the device's
+    inf = ImageInference(seed=1234, device=dev, precision='f16')
+
+    def run(resize, convert):
+        inf.resize, inf.convert = resize, convert
+        items = [inf.route(im) for im in images]
+        made = ['native' if isinstance(it, Native) else 'ragged' if it[1] else it[0].shape for it in items]
+        return made, [t.cpu().numpy() for t in inf.forward_routed(items)]
+
+    F, G1, G3 = (48, 48, 1), (224, 224, 1), (224, 224, 3)
+    run('host', 'host')  # the handle's GEMM autotuner settles on this first pass
+    made_h, ref = run('host', 'host')
+    assert made_h == [G3, F, G1, G3, F, G3, G1, G3, G1]
+    made_r, got_r = run('gpu', 'host')
+    assert made_r == ['ragged', F, 'ragged', G3, F, 'ragged', G1, 'ragged', 'ragged']
+    made_c, got_c = run('gpu', 'gpu')
+    assert made_c == ['native', F, 'native', G3, 'native', 'ragged', G1, 'native', 'native']
+    assert ref[0].shape == (9, 512) and ref[1].shape == (9, 7)
+    for got in (got_r, got_c):
+        assert np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1])
+
+
 def test_predict_and_extract_features_on_files(dev, tmp_path):
     from PIL import Image
     from inference.image_inference import ImageInference
