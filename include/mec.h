@@ -86,6 +86,41 @@ int mec_create_opt(int kind, const float* host_blob, size_t n, int device, int p
  * "" for other precisions, NULL on a null handle. Owned by the handle (valid until mec_destroy). For
  * diagnosing a range-flag failure (mec_model_check returning MEC_ERR_X3_RANGE). */
 const char* mec_model_x3_report(mec_model* m);
+
+/* Calibration of the image kinds' fp32x3 plane exponents (MEC_IMAGE, MEC_IMAGE_MBV2) from observed data. By
+ * default those exponents come from a BatchNorm estimate (above); a checkpoint whose activations do not follow
+ * it either trips the range flag or sits far below the planes' 2^-3 floor unnoticed. The tensors concerned are
+ * the lines of mec_model_x3_report, in its order: ResNet50's 37 ("stem", then per stage "layerN.out" and per
+ * block "layerN.k.conv1", "layerN.k.conv2"), MobileNetV2's 7 ("featuresA-B.out"); "layerN.out" and
+ * "featuresA-B.out" stand for every block output of the stage, which share one exponent.
+ *   1. mec_model_x3_observe(m32, 1) on an MEC_PREC_FP32 handle m32 of the same kind and weights: allocates and
+ *      zeroes one slot per tensor and arms the forward's taps (synchronizes the device). Returns the tensor
+ *      count n. While armed, every forward of m32 reduces each of those tensors to max |x| on its stream (one
+ *      small HBM-bound launch per tensor) into the tensor's slot; a slot keeps the running maximum over all
+ *      forwards since it was armed. The forward's outputs are the same bits armed or not.
+ *      mec_model_x3_observe(m32, 0) disarms (no launch is added to a forward; the slots stay readable) and
+ *      returns n as well. -1 for any other handle.
+ *   2. mec_model_x3_observed(m32, absmax, cap): synchronizes the device and copies the n maxima in report order
+ *      to the host array absmax (cap >= n entries); returns n, -1 if the handle was never armed or cap < n. A
+ *      tensor that held an inf or a NaN reads +inf. mec_model_x3_names(m): the n names, one per line, for any
+ *      handle of the two kinds (owned by the handle; NULL on error).
+ *   3. mec_create_x3_calibrated(kind, blob, n, device, opts, absmax, count, &m): an MEC_PREC_FP32X3 handle
+ *      exactly as mec_create_opt creates it, except that a tensor with absmax[i] > 0 takes its exponent from
+ *      that observed maximum in place of the estimate, against the same target (2^10: 64x headroom to the f16
+ *      range, kept because a calibration batch is a sample of the data; "x3_headroom" applies on top).
+ *      absmax[i] == 0 (a dead tensor) keeps the estimate. Epilogue scales, scaled biases and the dual GEMM's
+ *      pre-scale follow from the exponents as always. Its mec_model_x3_report has "x3_calibrated=1" on the
+ *      first line and the observed value as the line's bound=. Returns -1 before any device call for a kind
+ *      other than the two, count != n, a null absmax or out, and a negative, NaN or inf value. */
+int mec_model_x3_observe(mec_model* m, int on);
+int mec_model_x3_observed(mec_model* m, float* absmax_host, int cap);
+const char* mec_model_x3_names(mec_model* m);
+int mec_create_x3_calibrated(int kind, const float* host_blob, size_t n, int device, const char* opts,
+                             const float* absmax, int count, mec_model** out);
+/* The taps' reduction on its own: max |x| over n floats at x_dev (device, 4-byte aligned) -> *out_host, +inf
+ * if any is an inf or a NaN; synchronizes `stream`. n == 0 gives 0.0 without a launch. The maximum is taken
+ * on the bit patterns, so it is exact and the same at any launch geometry. */
+int mec_absmax_f32(const float* x_dev, long long n, float* out_host, void* stream);
 /* The handle's precision (MEC_PREC_*), -1 on a null handle. */
 int mec_precision(const mec_model* m);
 int mec_destroy(mec_model* m);

@@ -2,6 +2,7 @@
 #include "../../include/mec.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <exception>
 #include <new>
@@ -71,6 +72,14 @@ size_t blob_floats(int kind) {
     default: return 0;
   }
 }
+
+// Tensors with an fp32x3 plane exponent taken from a BN estimate (image_model.h resnet_x3_tensors /
+// mb_x3_tensors), known before a handle exists; 0: the kind has none
+static int x3_tensor_count(int kind) {
+  if (kind == KIND_IMAGE) return 1 + 4 + 2 * (3 + 4 + 6 + 3);  // stem, layerN.out, conv1 + conv2 per block
+  if (kind == KIND_IMAGE_MBV2) return 7;                      // one per (t, c, n, s) setting
+  return 0;
+}
 }  // namespace mec
 
 using namespace mec;
@@ -92,12 +101,84 @@ static ImageNet* image_net(mec_model* m) {
   return static_cast<ImageNet*>(m->impl);
 }
 
+// The observation entry points take an exact-fp32 handle of either backbone: its forward is what is observed.
+static ImageNet* observed_net(mec_model* m, const char* who) {
+  if (!m || !m->impl || (m->impl->kind != KIND_IMAGE && m->impl->kind != KIND_IMAGE_MBV2) || m->impl->prec != PREC_FP32) {
+    set_error(std::string(who) + ": needs an MEC_PREC_FP32 handle of kind MEC_IMAGE or MEC_IMAGE_MBV2");
+    return nullptr;
+  }
+  return image_net(m);
+}
+
 template <class T>
 static T* as(mec_model* m, int kind) {
   if (!m || !m->impl) { set_error("null model handle"); return nullptr; }
   if (m->impl->kind != kind) { set_error("model handle has the wrong kind for this call"); return nullptr; }
   if (hipSetDevice(m->impl->device) != hipSuccess) { set_error("hipSetDevice failed"); return nullptr; }
   return static_cast<T*>(m->impl);
+}
+
+// mec_create_opt's body; cal (or null): the observed maxima of a calibrated creation, already checked
+static int create_model(int kind, const float* host_blob, size_t n, int device, int precision, const char* opts,
+                        const std::vector<double>* cal, mec_model** out) {
+  if (!out) { set_error("mec_create: out is null"); return -1; }
+  if (precision != MEC_PREC_F16 && precision != MEC_PREC_FP32 && precision != MEC_PREC_FP32X3) {
+    set_error("mec_create: precision must be MEC_PREC_F16, MEC_PREC_FP32 or MEC_PREC_FP32X3");
+    return -1;
+  }
+  *out = nullptr;
+  const size_t want = blob_floats(kind);
+  if (!want) { set_error("mec_create: unknown kind"); return -1; }
+  if (!host_blob || n != want) {
+    set_error("mec_create: blob has " + std::to_string(n) + " floats, expected " + std::to_string(want));
+    return -1;
+  }
+  // "key=value,key=value": this handle's knobs, applied over the process defaults before its weights are
+  // packed (so creation-time knobs such as x3_headroom take effect)
+  Options o = default_options();
+  if (opts && *opts) {
+    std::string all(opts);
+    size_t pos = 0;
+    while (pos <= all.size()) {
+      const size_t end = std::min(all.find(',', pos), all.size());
+      const std::string kv = all.substr(pos, end - pos);
+      const size_t eq = kv.find('=');
+      if (eq == std::string::npos || eq == 0) { set_error("mec_create_opt: bad option \"" + kv + "\" (key=value)"); return -1; }
+      char* tail = nullptr;
+      const long v = std::strtol(kv.c_str() + eq + 1, &tail, 10);
+      if (!tail || *tail || tail == kv.c_str() + eq + 1) { set_error("mec_create_opt: bad value in \"" + kv + "\""); return -1; }
+      if (set_option(o, kv.substr(0, eq), (int)v) != 0) return -1;
+      pos = end + 1;
+    }
+  }
+  MEC_HIP(hipSetDevice(device));
+  Model* impl = nullptr;
+  int rc = -1;
+  switch (kind) {
+    // speech, fusion, audio and the BiLSTM are fp32 at every precision
+    case KIND_SPEECH: { auto* p = new SpeechModel(); impl = p; p->opts = o; rc = p->create(host_blob, n); break; }
+    case KIND_TEXT: { auto* p = new TextModel(); p->prec = precision; impl = p; p->opts = o; rc = p->create(host_blob, n); break; }
+    case KIND_IMAGE: { auto* p = new ImageModel(); p->prec = precision; impl = p; p->opts = o; if (cal) p->x3_cal = *cal; rc = p->create(host_blob, n); break; }
+    case KIND_FUSION: { auto* p = new FusionModel(); impl = p; p->opts = o; rc = p->create(host_blob, n); break; }
+    case KIND_IMAGE_MBV2: { auto* p = new MobileNetModel(); p->prec = precision; impl = p; p->opts = o; if (cal) p->x3_cal = *cal; rc = p->create(host_blob, n); break; }
+    case KIND_AUDIO: { auto* p = new AudioModel(); impl = p; p->opts = o; rc = p->create(host_blob, n); break; }
+    case KIND_TEXT_LSTM: { auto* p = new LstmTextModel(); impl = p; p->opts = o; rc = p->create(host_blob, n); break; }
+  }
+  if (rc != 0) { delete impl; return -1; }
+  if (cal && impl->x3_noted != cal->size()) {  // x3_tensor_count and the creation disagree
+    set_error("mec_create_x3_calibrated: the creation named " + std::to_string(impl->x3_noted) + " tensors");
+    delete impl;
+    return -1;
+  }
+  impl->kind = kind;
+  impl->device = device;
+  impl->prec = (kind == KIND_SPEECH || kind == KIND_FUSION || kind == KIND_AUDIO || kind == KIND_TEXT_LSTM) ? MEC_PREC_FP32 : precision;
+  if (impl->prec == PREC_FP32X3 && impl->alloc_range_flag() != 0) { delete impl; return -1; }
+  if (impl->prec == PREC_FP32X3)
+    impl->x3_report = "x3_headroom=" + std::to_string(o.x3_headroom) + " x3_plane_scale=" +
+                      std::to_string(o.x3_plane_scale) + (cal ? " x3_calibrated=1" : "") + "\n" + impl->x3_report;
+  *out = new mec_model{impl};
+  return 0;
 }
 
 extern "C" {
@@ -120,66 +201,90 @@ int mec_create_ex(int kind, const float* host_blob, size_t n, int device, int pr
 
 int mec_create_opt(int kind, const float* host_blob, size_t n, int device, int precision, const char* opts,
                    mec_model** out) {
+  API_GUARD({ return create_model(kind, host_blob, n, device, precision, opts, nullptr, out); })
+}
+
+int mec_create_x3_calibrated(int kind, const float* host_blob, size_t n, int device, const char* opts,
+                             const float* absmax, int count, mec_model** out) {
   API_GUARD({
-    if (!out) { set_error("mec_create: out is null"); return -1; }
-    if (precision != MEC_PREC_F16 && precision != MEC_PREC_FP32 && precision != MEC_PREC_FP32X3) {
-      set_error("mec_create: precision must be MEC_PREC_F16, MEC_PREC_FP32 or MEC_PREC_FP32X3");
-      return -1;
-    }
+    if (!out) { set_error("mec_create_x3_calibrated: out is null"); return -1; }
     *out = nullptr;
-    const size_t want = blob_floats(kind);
-    if (!want) { set_error("mec_create: unknown kind"); return -1; }
-    if (!host_blob || n != want) {
-      set_error("mec_create: blob has " + std::to_string(n) + " floats, expected " + std::to_string(want));
+    const int want = x3_tensor_count(kind);
+    if (!want) {
+      set_error("mec_create_x3_calibrated: kind must be MEC_IMAGE or MEC_IMAGE_MBV2 (the plane exponents of the "
+                "other kinds come from rigorous bounds, or the kind has no fp32x3 path)");
       return -1;
     }
-    // "key=value,key=value": this handle's knobs, applied over the process defaults before its weights are
-    // packed (so creation-time knobs such as x3_headroom take effect)
-    Options o = default_options();
-    if (opts && *opts) {
-      std::string all(opts);
-      size_t pos = 0;
-      while (pos <= all.size()) {
-        const size_t end = std::min(all.find(',', pos), all.size());
-        const std::string kv = all.substr(pos, end - pos);
-        const size_t eq = kv.find('=');
-        if (eq == std::string::npos || eq == 0) { set_error("mec_create_opt: bad option \"" + kv + "\" (key=value)"); return -1; }
-        char* tail = nullptr;
-        const long v = std::strtol(kv.c_str() + eq + 1, &tail, 10);
-        if (!tail || *tail || tail == kv.c_str() + eq + 1) { set_error("mec_create_opt: bad value in \"" + kv + "\""); return -1; }
-        if (set_option(o, kv.substr(0, eq), (int)v) != 0) return -1;
-        pos = end + 1;
+    if (!absmax) { set_error("mec_create_x3_calibrated: absmax is null"); return -1; }
+    if (count != want) {
+      set_error("mec_create_x3_calibrated: count is " + std::to_string(count) + ", this kind has " +
+                std::to_string(want) + " tensors (mec_model_x3_names)");
+      return -1;
+    }
+    std::vector<double> cal(absmax, absmax + count);
+    for (int i = 0; i < count; ++i)
+      if (!(cal[i] >= 0.0) || !std::isfinite(cal[i])) {
+        set_error("mec_create_x3_calibrated: absmax[" + std::to_string(i) + "] is negative, NaN or inf (an observed "
+                  "maximum is finite and >= 0; 0 keeps the tensor's estimate)");
+        return -1;
       }
-    }
-    MEC_HIP(hipSetDevice(device));
-    Model* impl = nullptr;
-    int rc = -1;
-    switch (kind) {
-      // speech, fusion, audio and the BiLSTM are fp32 at every precision
-      case KIND_SPEECH: { auto* p = new SpeechModel(); impl = p; p->opts = o; rc = p->create(host_blob, n); break; }
-      case KIND_TEXT: { auto* p = new TextModel(); p->prec = precision; impl = p; p->opts = o; rc = p->create(host_blob, n); break; }
-      case KIND_IMAGE: { auto* p = new ImageModel(); p->prec = precision; impl = p; p->opts = o; rc = p->create(host_blob, n); break; }
-      case KIND_FUSION: { auto* p = new FusionModel(); impl = p; p->opts = o; rc = p->create(host_blob, n); break; }
-      case KIND_IMAGE_MBV2: { auto* p = new MobileNetModel(); p->prec = precision; impl = p; p->opts = o; rc = p->create(host_blob, n); break; }
-      case KIND_AUDIO: { auto* p = new AudioModel(); impl = p; p->opts = o; rc = p->create(host_blob, n); break; }
-      case KIND_TEXT_LSTM: { auto* p = new LstmTextModel(); impl = p; p->opts = o; rc = p->create(host_blob, n); break; }
-    }
-    if (rc != 0) { delete impl; return -1; }
-    impl->kind = kind;
-    impl->device = device;
-    impl->prec = (kind == KIND_SPEECH || kind == KIND_FUSION || kind == KIND_AUDIO || kind == KIND_TEXT_LSTM) ? MEC_PREC_FP32 : precision;
-    if (impl->prec == PREC_FP32X3 && impl->alloc_range_flag() != 0) { delete impl; return -1; }
-    if (impl->prec == PREC_FP32X3)
-      impl->x3_report = "x3_headroom=" + std::to_string(o.x3_headroom) + " x3_plane_scale=" +
-                        std::to_string(o.x3_plane_scale) + "\n" + impl->x3_report;
-    *out = new mec_model{impl};
-    return 0;
+    return create_model(kind, host_blob, n, device, MEC_PREC_FP32X3, opts, &cal, out);
   })
 }
 
 const char* mec_model_x3_report(mec_model* m) {
   if (!m || !m->impl) { set_error("mec_model_x3_report: null handle"); return nullptr; }
   return m->impl->x3_report.c_str();
+}
+
+const char* mec_model_x3_names(mec_model* m) {
+  try {
+    ImageNet* p = image_net(m);
+    if (!p) return nullptr;
+    if (p->x3_names.empty())
+      for (const std::string& name : p->x3_tensors().names) p->x3_names += name + "\n";
+    return p->x3_names.c_str();
+  } catch (const std::exception& e) {
+    set_error(e.what());
+    return nullptr;
+  }
+}
+
+int mec_model_x3_observe(mec_model* m, int on) {
+  API_GUARD({
+    ImageNet* p = observed_net(m, "mec_model_x3_observe");
+    if (!p) return -1;
+    MEC_REQUIRE(on == 0 || on == 1, "mec_model_x3_observe: on is 0 or 1");
+    if (on) {
+      const int n = (int)p->x3_tensors().names.size();
+      MEC_HIP(hipDeviceSynchronize());  // no forward of the handle may still fill the slots
+      MEC_TRY(p->obs.ensure(n * sizeof(unsigned)));
+      MEC_HIP(hipMemset(p->obs.p, 0, n * sizeof(unsigned)));
+      MEC_HIP(hipDeviceSynchronize());
+      p->obs_n = n;
+    }
+    p->obs_on = on != 0;
+    return p->obs_n;
+  })
+}
+
+int mec_model_x3_observed(mec_model* m, float* absmax_host, int cap) {
+  API_GUARD({
+    ImageNet* p = observed_net(m, "mec_model_x3_observed");
+    if (!p) return -1;
+    MEC_REQUIRE(p->obs_n > 0, "mec_model_x3_observed: the handle was never armed (mec_model_x3_observe(m, 1))");
+    MEC_REQUIRE(absmax_host && cap >= p->obs_n, "mec_model_x3_observed: absmax_host must hold the handle's tensor "
+                                                "count (what mec_model_x3_observe returned)");
+    MEC_HIP(hipDeviceSynchronize());
+    std::vector<unsigned> bits(p->obs_n);
+    MEC_HIP(hipMemcpy(bits.data(), p->obs.p, bits.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+    for (int i = 0; i < p->obs_n; ++i) absmax_host[i] = absmax_from_bits(bits[i]);
+    return p->obs_n;
+  })
+}
+
+int mec_absmax_f32(const float* x_dev, long long n, float* out_host, void* stream) {
+  API_GUARD({ return absmax_f32(x_dev, n, out_host, S(stream)); })
 }
 
 int mec_destroy(mec_model* m) {

@@ -4,6 +4,7 @@
 // packed fields feed a conv, the launch function, and what may take over a block's end. Host code only.
 #pragma once
 #include <algorithm>
+#include <string>
 
 #include "block_ops.h"
 #include "models.h"
@@ -64,6 +65,34 @@ static inline void conv_geometry(GemmParams& g, int H, int C, int OH, int ks, in
   g.H = H; g.W = H; g.C = C; g.OH = OH; g.OW = OH; g.ks = ks; g.stride = stride; g.pad = pad;
 }
 
+// The tensors with an fp32x3 plane exponent (models.h X3Tensors): the stem output, then per stage (a block with a
+// downsample opens one) the residual stream "layerN.out", shared by the stage's block outputs, and each block's
+// conv1 / conv2 outputs. The fp32x3 creation names its exponents from this list and an observing fp32 forward
+// fills one slot per entry (RnTap).
+static inline X3Tensors resnet_x3_tensors(const std::vector<Bottleneck>& blocks) {
+  X3Tensors t;
+  t.names.push_back("stem");
+  int stage = 1;
+  for (size_t b0 = 0; b0 < blocks.size(); ++stage) {
+    size_t b1 = b0 + 1;
+    while (b1 < blocks.size() && !blocks[b1].has_ds) ++b1;  // [b0, b1): one stage
+    const std::string st = "layer" + std::to_string(stage);
+    const int out = (int)t.names.size();
+    t.names.push_back(st + ".out");
+    for (size_t bi = b0; bi < b1; ++bi) {
+      const std::string bn = st + "." + std::to_string(bi - b0);
+      t.out.push_back(out);
+      t.c1.push_back((int)t.names.size());
+      t.names.push_back(bn + ".conv1");
+      t.c2.push_back((int)t.names.size());
+      t.names.push_back(bn + ".conv2");
+    }
+    b0 = b1;
+  }
+  return t;
+}
+enum RnTap : int { TAP_CONV1, TAP_CONV2, TAP_OUT };
+
 // What a policy's block_end sees once conv2 has run: it may run conv3 (+ downsample | + identity) + ReLU and the
 // next block's conv1 in one seam kernel (returns 1; 0: not taken, the walk runs the GEMMs; -1: error).
 struct RnBlockEnd {
@@ -82,6 +111,8 @@ struct RnBlockEnd {
 //   kDualDs                                  the downsample rides in conv3's GEMM (A_DUAL), else its own GEMM into DS
 //   kChunked                                 opt().resnet_chunk applies
 //   block_end(e, t2, in, out)                see RnBlockEnd
+//   kTap, tap(which, bi, x, n)               fp32: block bi's finished conv1 / conv2 / output tensor x of n elements
+//                                            (RnTap) is offered to the observation (a no-op unless armed)
 //
 // Bottleneck blocks [b0, b1) over images [i0, i0 + nb) of the batch (NHWC buffers are image-major, so an image
 // range is a pointer offset; fp32x3 lo planes stay L elements after their hi planes). cur/other swap once per
@@ -104,6 +135,7 @@ int resnet_walk(const std::vector<Bottleneck>& blocks, Pol& p, size_t b0, size_t
       p.a(g, in); p.w(g, bk.c1); p.c(g, t1); g.act = ACT_RELU;
       g.M = nb * H * H; g.N = wd; g.K = cin;
       MEC_TRY(p.launch(g, &p.prof, TAG_RESNET_CONV1X1));
+      if constexpr (Pol::kTap) MEC_TRY(p.tap(TAP_CONV1, bi, t1, (size_t)nb * H * H * wd));
     }
     conv1_done = false;
     g = GemmParams();
@@ -111,6 +143,7 @@ int resnet_walk(const std::vector<Bottleneck>& blocks, Pol& p, size_t b0, size_t
     g.M = M; g.N = wd; g.K = 9 * wd;
     conv_geometry(g, H, wd, OH, 3, st, 1);
     MEC_TRY(p.launch(g, &p.prof, TAG_RESNET_CONV3X3));
+    if constexpr (Pol::kTap) MEC_TRY(p.tap(TAP_CONV2, bi, t2, (size_t)M * wd));
     const Bottleneck* nx = bi + 1 < b1 ? &blocks[bi + 1] : nullptr;
     const Bottleneck* nxc = nx ? nx : (cross && bi + 1 < blocks.size() ? &blocks[bi + 1] : nullptr);
     const int fused = p.block_end(RnBlockEnd{bk, nx, nxc, wd, cin, st, OH, M, (size_t)i0 * OH * OH}, t2, in, out);
@@ -141,6 +174,7 @@ int resnet_walk(const std::vector<Bottleneck>& blocks, Pol& p, size_t b0, size_t
       p.c(g, out); g.act = ACT_RELU; g.M = M; g.N = 4 * wd;
       MEC_TRY(p.launch(g, &p.prof, TAG_RESNET_CONV1X1));
     }
+    if constexpr (Pol::kTap) MEC_TRY(p.tap(TAP_OUT, bi, out, (size_t)M * 4 * wd));
     std::swap(cur, other);
     H = OH;
   }
@@ -176,6 +210,20 @@ constexpr int kMbFeat = 1280;
 
 static inline int mb_out_side(const MbBlock& b, int h) { return b.stride == 2 ? h / 2 : h; }
 static inline bool mb_residual(const MbBlock& b) { return b.stride == 1 && b.cin == b.cout; }
+
+// The tensors with an fp32x3 plane exponent (models.h X3Tensors): one per stage, "featuresA-B.out", shared by the
+// outputs of blocks[A - 1 .. B - 1] (features[A .. B]); a stage runs from a block without a residual to the next one
+static inline X3Tensors mb_x3_tensors(const std::vector<MbBlock>& blocks) {
+  X3Tensors t;
+  for (size_t b0 = 0; b0 < blocks.size();) {
+    size_t b1 = b0 + 1;
+    while (b1 < blocks.size() && mb_residual(blocks[b1])) ++b1;
+    for (size_t i = b0; i < b1; ++i) t.out.push_back((int)t.names.size());
+    t.names.push_back("features" + std::to_string(b0 + 1) + "-" + std::to_string(b1) + ".out");
+    b0 = b1;
+  }
+  return t;
+}
 
 // Layered tail: blocks[l0 ..] (features[l0 + 1 ..]) run as expand GEMM -> depthwise -> project GEMM. knob names
 // features[k] (0: none); last_always: the last block has no fused form and is layered at every setting.
@@ -227,6 +275,7 @@ void mb_fused_args(Args& a, const MobileNetModel& m, const MbBlock& b, const voi
 //   project(g, b, i, res, out)  the same for the project GEMM (D -> out, + res when not null)
 //   last(g, in)                 and for features[18]
 //   launch(g, prof, tag)        the GEMM engine
+//   kTap, tap(i, x, n)          fp32: block i's finished output x of n elements is offered to the observation
 // One block: [expand 1x1 + BN + ReLU6] -> depthwise 3x3/s + BN + ReLU6 -> project 1x1 + BN (+ the block input).
 // Untagged launches: inside the TAG_MBV2_BLOCK window.
 template <class Pol>
@@ -242,7 +291,9 @@ int mb_block(Pol& p, const MbBlock& b, size_t i, int B, int h, const typename Po
   MEC_TRY(p.depthwise(b, B, h, oh, in));
   p.project(g, b, i, mb_residual(b) ? in : nullptr, out);
   g.M = B * oh * oh; g.N = mb_nout<Pol::kLayered>(b); g.K = b.hidp;
-  return p.launch(g, nullptr, TAG_NONE);
+  MEC_TRY(p.launch(g, nullptr, TAG_NONE));
+  if constexpr (Pol::kTap) MEC_TRY(p.tap(i, out, (size_t)g.M * g.N));
+  return 0;
 }
 
 // features[18] 1x1 320 -> 1280 + BN + ReLU6

@@ -810,7 +810,7 @@ __global__ __launch_bounds__(256) void mbv2_pad_f16_kernel(const f16* __restrict
 // f16 policy of the layered blocks (image_model.h): f16 rows of lcinp / lcoutp channels, the layered matrices
 struct MbF16 {
   using IO = f16;
-  static constexpr bool kLayered = true;
+  static constexpr bool kLayered = true, kTap = false;
   const MobileNetModel& m;
   const f16* Wt;
   const float* P;

@@ -115,14 +115,18 @@ int MobileNetModel::create_f32(const float* blob, size_t n) {
 }
 
 // fp32 policy of a block (image_model.h): f32 rows of cinp / coutp channels (padded to 64), f32 weights on gemm_f32
+// obs (null: disarmed, no launch): the observation's slots, one per tensor of xt (mec_model_x3_observe)
 struct MbF32 {
   using IO = float;
-  static constexpr bool kLayered = false;
+  static constexpr bool kLayered = false, kTap = true;
   const MobileNetModel& m;
   const float *Wt, *P;
   Prof& prof;
   hipStream_t s;
   float *E, *D, *L;
+  unsigned* obs;
+  const X3Tensors& xt;
+  int tap(size_t i, const float* x, size_t n) const { return obs ? launch_absmax_f32(x, n, obs + xt.out[i], s) : 0; }
   void expand(GemmParams& g, const MbBlock& b, size_t, const float* in) const {
     g.A = in; g.B32 = Wt + b.we_off; g.bias = P + b.be_off; g.C32 = E;
   }
@@ -140,6 +144,8 @@ struct MbF32 {
   void last(GemmParams& g, const float* in) const { g.A = in; g.B32 = Wt + m.last_w_off; g.bias = P + m.last_b_off; g.C32 = L; }
   int launch(const GemmParams& g, Prof* pr, int tag) const { return launch_gemm_f32(g, s, pr, tag); }
 };
+
+X3Tensors MobileNetModel::x3_tensors() const { return mb_x3_tensors(blocks); }
 
 int MobileNetModel::forward_f32(const uint8_t* img, int B, int H, int W, int C, float* feat, float* logits,
                                 float* probs, hipStream_t s) {
@@ -160,7 +166,8 @@ int MobileNetModel::forward_f32(const uint8_t* img, int B, int H, int W, int C, 
     Lst = c.take<float>(B * kMbLast);
     pooled = c.take<float>((size_t)B * kMbFeat);
   }));
-  MbF32 p{*this, wts32.as<float>(), prm.as<float>(), prof, s, E, D, Lst};
+  const X3Tensors xt = obs_on ? x3_tensors() : X3Tensors();
+  MbF32 p{*this, wts32.as<float>(), prm.as<float>(), prof, s, E, D, Lst, obs_on ? obs.as<unsigned>() : nullptr, xt};
   StemIn in;
   MEC_TRY(image_stem_input(img, B, H, W, C, resized, s, in));
   MEC_TRY(prof.begin(TAG_MBV2_BLOCK, s));

@@ -649,18 +649,19 @@ int MobileNetModel::create_x3(const float* blob, size_t n) {
   // along the residual chain. Block inputs are the previous stage's planes; the depthwise outputs are at
   // kDwUp. Every epilogue scale below folds in 2^(s_out - s_in) (the fused blocks' and the expand GEMMs'
   // outputs are f32: s_out = 0 there).
+  // A calibrated creation (x3_tensor) takes a stage's observed maximum in place of its estimate.
   {
+    const X3Tensors xt = x3_tensors();
     int s_prev = 0;
     for (size_t b0 = 0; b0 < blocks.size();) {
       size_t b1 = b0 + 1;
-      while (b1 < blocks.size() && blocks[b1].stride == 1 && blocks[b1].cin == blocks[b1].cout) ++b1;
+      while (b1 < blocks.size() && xt.out[b1] == xt.out[b0]) ++b1;  // [b0, b1): one stage
       double e = 0.0, e_max = 0.0;
       for (size_t i = b0; i < b1; ++i) {
         e = blocks[i].x3_est + (i > b0 ? e : 0.0);
         e_max = std::max(e_max, e);
       }
-      const int st = x3_exp(e_max, kX3EstimateTarget);
-      x3_note("features" + std::to_string(b0 + 1) + "-" + std::to_string(b1) + ".out", st, e_max);
+      const int st = x3_tensor(xt.names[xt.out[b0]], e_max, kX3EstimateTarget);
       for (size_t i = b0; i < b1; ++i) {
         blocks[i].x3_s_in = i == b0 ? s_prev : st;
         blocks[i].x3_s_out = st;
@@ -696,7 +697,7 @@ int MobileNetModel::create_x3(const float* blob, size_t n) {
 // planes plo / dlo halfs after the hi planes), E in f32, the layered matrices' planes with their epilogue scales
 struct MbX3 {
   using IO = f16;
-  static constexpr bool kLayered = true;
+  static constexpr bool kLayered = true, kTap = false;
   const MobileNetModel& m;
   const f16* Wt;
   long long wlo, plo, dlo;

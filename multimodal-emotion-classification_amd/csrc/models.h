@@ -40,6 +40,12 @@ struct Model {
   // the exponent this handle gives an activation tensor: activation_exp (below) against 2^-x3_headroom of
   // the target (a handle re-created after a range trip), or 0 with x3_plane_scale off (unscaled planes, A/B only)
   int x3_exp(double bound, double target) const;
+  // Calibrated creation (mec_create_x3_calibrated; the image kinds): x3_cal holds one observed max |x| per
+  // tensor in report order, and x3_tensor -- the exponent of the next tensor of that order, noted under `name`
+  // -- takes a finite x3_cal[i] > 0 in place of the BN estimate `est` (0, a dead tensor: the estimate stays)
+  std::vector<double> x3_cal;
+  size_t x3_noted = 0;
+  int x3_tensor(const std::string& name, double est, double target);
   virtual ~Model();
   // errors a kernel could only report after the fact (mec_model_check): 0 = none since the last
   // check. Call after the stream that ran the handle's forwards has been synchronized.
@@ -229,7 +235,23 @@ int lstm_seq_f32(const float* xz, const float* U, int B, int L, int units, int r
 // workspace carve, the optional 48 -> 224 resize, the precision's own stem, the walk over the backbone's blocks
 // under that precision's policy, the precision's average pool, then the output tail (fc1 + ReLU = the feature,
 // logits, probs).
+// The activation tensors the fp32x3 creation of an image kind gives a plane exponent, in mec_model_x3_report's
+// order (image_model.h resnet_x3_tensors / mb_x3_tensors), and where block i's tensors stand in that list: its
+// output (a stage's blocks share one entry, "layerN.out" / "featuresA-B.out") and, ResNet50, its conv1 / conv2
+struct X3Tensors {
+  std::vector<std::string> names;
+  std::vector<int> out, c1, c2;
+};
+
 struct ImageNet : Model {
+  // Observation (mec_model_x3_observe; fp32 handles): while obs_on, forward_f32 reduces every tensor of
+  // x3_tensors() to max |x| (absmax.hip) on its stream, into that tensor's slot of obs (float bits, unsigned
+  // [obs_n]); a slot keeps the running maximum across forwards until observation is armed again
+  DevBuf obs;
+  int obs_n = 0;
+  bool obs_on = false;
+  virtual X3Tensors x3_tensors() const = 0;
+  std::string x3_names;  // its names, one per line (mec_model_x3_names; built on first use)
   // img u8 [B,H,W,C]: (48,48,1) gray FER2013 (GPU resize), (224,224,1) gray, (224,224,3) RGB
   virtual int forward_u8(const uint8_t* img, int B, int H, int W, int C, float* feat, float* logits, float* probs,
                          hipStream_t s) = 0;
@@ -289,6 +311,7 @@ struct ImageModel : ImageNet {
   DevBuf wts_dual;  // fp32x3: block 0's [conv3 | downsample] hi / lo planes (c3ds_w_off, c3ds_x3_lo)
   int forward_x3(const uint8_t* img, int B, int H, int W, int C, float* feat, float* logits, float* probs,
                  hipStream_t s);
+  X3Tensors x3_tensors() const override;
 };
 
 // ---------------------------------------------------------------- MobileNetV2 + head
@@ -337,7 +360,14 @@ struct MobileNetModel : ImageNet {
   int create_x3(const float* blob, size_t n);
   int forward_x3(const uint8_t* img, int B, int H, int W, int C, float* feat, float* logits, float* probs,
                  hipStream_t s);
+  X3Tensors x3_tensors() const override;
 };
+
+// max |x| of n floats into *slot as float bits, by atomicMax: the running maximum since the slot was zeroed
+// (absmax.hip); absmax_from_bits: a slot's value, +inf for an inf or a NaN; absmax_f32: mec_absmax_f32
+int launch_absmax_f32(const float* x, size_t n, unsigned* slot, hipStream_t s);
+float absmax_from_bits(unsigned bits);
+int absmax_f32(const float* x_dev, long long n, float* out_host, hipStream_t s);
 
 int resize_u8(const uint8_t* in, int B, int H, int W, uint8_t* out, int OH, int OW, hipStream_t s);
 // layer1 seam: conv3 (64 -> 256) + residual + ReLU, then the next block's conv1 (256 -> N2)

@@ -433,7 +433,7 @@ int ImageModel::create(const float* blob, size_t n) {
 // conv3 + downsample as one dual-K GEMM; the layer1 seam kernels (pw_chain.hip) may take over a block's end.
 struct RnF16 {
   using T = f16;
-  static constexpr bool kDualDs = true, kChunked = true;
+  static constexpr bool kDualDs = true, kChunked = true, kTap = false;
   const f16* Wt;
   const float* P;
   Prof& prof;

@@ -420,11 +420,11 @@ int ImageModel::create_f32(const float* blob, size_t n) {
     // add commute with the power of two: the f32 values are the unscaled ones times 2^s_out exactly).
     // The downsample of a stage's first block reads the block input (s_in) beside conv3's T2 (s_t2)
     // in one dual GEMM: its weights are pre-scaled by 2^(s_t2 - s_in) so both halves of K carry 2^s_t2.
-    stem.x3_s = x3_exp(stem.x3_est, kX3EstimateTarget);
-    x3_note("stem", stem.x3_s, stem.x3_est);
+    // A calibrated creation (x3_tensor) takes a tensor's observed maximum in place of its estimate.
+    const X3Tensors xt = x3_tensors();
+    stem.x3_s = x3_tensor(xt.names[0], stem.x3_est, kX3EstimateTarget);
     {
       int s_prev = stem.x3_s;
-      int stage = 0;
       double e_stream = stem.x3_est;
       for (size_t b0 = 0; b0 < blocks.size();) {
         size_t b1 = b0 + 1;
@@ -435,20 +435,14 @@ int ImageModel::create_f32(const float* blob, size_t n) {
           e_stream = bk.c3.x3_est + (bk.has_ds ? bk.ds.x3_est : e_stream);
           e_max = std::max(e_max, e_stream);
         }
-        const int s_stage = x3_exp(e_max, kX3EstimateTarget);
-        const std::string st = "layer" + std::to_string(stage + 1);
-        x3_note(st + ".out", s_stage, e_max);
+        const int s_stage = x3_tensor(xt.names[xt.out[b0]], e_max, kX3EstimateTarget);
         for (size_t bi = b0; bi < b1; ++bi) {
           Bottleneck& bk = blocks[bi];
-          bk.c1.x3_s = x3_exp(bk.c1.x3_est, kX3EstimateTarget);
-          bk.c2.x3_s = x3_exp(bk.c2.x3_est, kX3EstimateTarget);
+          bk.c1.x3_s = x3_tensor(xt.names[xt.c1[bi]], bk.c1.x3_est, kX3EstimateTarget);
+          bk.c2.x3_s = x3_tensor(xt.names[xt.c2[bi]], bk.c2.x3_est, kX3EstimateTarget);
           bk.c3.x3_s = s_stage;
           bk.x3_s_in = bi == b0 ? s_prev : s_stage;
-          const std::string bn = st + "." + std::to_string(bi - b0);
-          x3_note(bn + ".conv1", bk.c1.x3_s, bk.c1.x3_est);
-          x3_note(bn + ".conv2", bk.c2.x3_s, bk.c2.x3_est);
         }
-        ++stage;
         s_prev = s_stage;
         b0 = b1;
       }
@@ -528,14 +522,22 @@ __global__ __launch_bounds__(256) void avgpool_split_kernel(const f16* __restric
 }
 
 // fp32 policy of the bottleneck walk (image_model.h): f32 NHWC operands and weights on gemm_f32, the downsample
-// as its own GEMM into DS, the whole batch at once, no seam kernels.
+// as its own GEMM into DS, the whole batch at once, no seam kernels. obs (null: disarmed, no launch): the
+// observation's slots, one per tensor of xt (mec_model_x3_observe).
 struct RnF32 {
   using T = float;
-  static constexpr bool kDualDs = false, kChunked = false;
+  static constexpr bool kDualDs = false, kChunked = false, kTap = true;
   const float *Wt, *P;
   Prof& prof;
   hipStream_t s;
   float *X, *Y, *Xs, *T1, *T2, *DS;
+  unsigned* obs;
+  const X3Tensors& xt;
+  int tap(int which, size_t bi, const float* x, size_t n) const {
+    if (!obs) return 0;
+    const int slot = which == TAP_CONV1 ? xt.c1[bi] : which == TAP_CONV2 ? xt.c2[bi] : xt.out[bi];
+    return launch_absmax_f32(x, n, obs + slot, s);
+  }
   void a(GemmParams& g, const float* p) const { g.A = p; }
   void c(GemmParams& g, float* p) const { g.C32 = p; }
   void r(GemmParams& g, const float* p) const { g.R = p; g.r_f32 = 1; }
@@ -543,6 +545,8 @@ struct RnF32 {
   int launch(const GemmParams& g, Prof* pr, int tag) const { return launch_gemm_f32(g, s, pr, tag); }
   int block_end(const RnBlockEnd&, float*, float*, float*) const { return 0; }
 };
+
+X3Tensors ImageModel::x3_tensors() const { return resnet_x3_tensors(blocks); }
 
 int ImageModel::forward_f32(const uint8_t* img, int B, int H, int W, int C, float* feat, float* logits, float* probs,
                             hipStream_t s) {
@@ -560,7 +564,8 @@ int ImageModel::forward_f32(const uint8_t* img, int B, int H, int W, int C, floa
     T2 = c.take<float>(B * kRnT2);
     pooled = c.take<float>((size_t)B * kRnFeat);
   }));
-  RnF32 p{wts32.as<float>(), prm.as<float>(), prof, s, X, Y, X, T1, T2, DS};
+  const X3Tensors xt = obs_on ? x3_tensors() : X3Tensors();
+  RnF32 p{wts32.as<float>(), prm.as<float>(), prof, s, X, Y, X, T1, T2, DS, obs_on ? obs.as<unsigned>() : nullptr, xt};
   StemIn in;
   MEC_TRY(image_stem_input(img, B, H, W, C, resized, s, in));
   MEC_TRY(prof.begin(TAG_RESNET_STEM, s));
@@ -588,6 +593,7 @@ int ImageModel::forward_f32(const uint8_t* img, int B, int H, int W, int C, floa
     hipLaunchKernelGGL(maxpool_f32_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, Y, B, 112, 64, 56, X);
     MEC_LAUNCH_CHECK();
   }
+  if (p.obs) MEC_TRY(launch_absmax_f32(X, B * kRnStem, p.obs, s));  // slot 0: the pooled stem output
   float* last;
   MEC_TRY(resnet_blocks(blocks, p, B, last));
   hipLaunchKernelGGL(avgpool_f32_kernel, dim3(B, kRnFeat / 256), dim3(256), 0, s, last, 7 * 7, kRnFeat, pooled);
@@ -609,7 +615,7 @@ int ImageModel::forward_f32(const uint8_t* img, int B, int H, int W, int C, floa
 // the layer1 and layer-2 seam kernels may take over a block's end.
 struct RnX3 {
   using T = f16;
-  static constexpr bool kDualDs = true, kChunked = true;
+  static constexpr bool kDualDs = true, kChunked = true, kTap = false;
   const f16 *Wt, *Wd;
   long long wlo, L;
   const float* P;

@@ -142,6 +142,14 @@ int Model::x3_exp(double bound, double target) const {
   return opts.x3_plane_scale ? activation_exp(bound, std::ldexp(target, -opts.x3_headroom)) : 0;
 }
 
+int Model::x3_tensor(const std::string& name, double est, double target) {
+  const size_t i = x3_noted++;
+  const double bound = i < x3_cal.size() && x3_cal[i] > 0.0 ? x3_cal[i] : est;
+  const int s = x3_exp(bound, target);
+  x3_note(name, s, bound);
+  return s;
+}
+
 float split_planes(const float* w, size_t n, f16* hi, f16* lo) {
   float mx = 0.f;
   for (size_t i = 0; i < n; ++i) mx = std::max(mx, std::fabs(w[i]));

@@ -263,6 +263,14 @@ class ImageInference:
         with Image.open(image_file_path) as im:
             return self._forward_image(im)
 
+    def calibrate(self, gray_batch):
+        """fp32x3 only: set the model's activation-plane exponents from an observed batch instead of the BatchNorm
+        estimate (engine.ImageEncoder.calibrate). gray_batch: device u8 [B,48,48] (or [B,H,W,C] as forward_u8 takes
+        it), or a list of such batches, representative of the data. -> {tensor name: (observed max |x|, exponent)}."""
+        if self.model is None:
+            raise RuntimeError('image model not loaded')
+        return self.model.calibrate(gray_batch)
+
     def predict_batch(self, gray):
         """gray: device u8 [B,48,48] -> (feat [B,512], logits [B,7], probs [B,7]). Asynchronous on the
         current stream, except on an fp32x3 handle: there it synchronizes and checks, so a batch outside

@@ -76,6 +76,12 @@ SIGNATURES = {
     'mec_create_ex': (c_int, [c_int, c_fp, ctypes.c_size_t, c_int, c_int, ctypes.POINTER(c_vp)]),
     'mec_create_opt': (c_int, [c_int, c_fp, ctypes.c_size_t, c_int, c_int, ctypes.c_char_p, ctypes.POINTER(c_vp)]),
     'mec_model_x3_report': (ctypes.c_char_p, [c_vp]),
+    'mec_model_x3_observe': (c_int, [c_vp, c_int]),
+    'mec_model_x3_observed': (c_int, [c_vp, c_fp, c_int]),
+    'mec_model_x3_names': (ctypes.c_char_p, [c_vp]),
+    'mec_create_x3_calibrated': (c_int, [c_int, c_fp, ctypes.c_size_t, c_int, ctypes.c_char_p, c_fp, c_int,
+                                         ctypes.POINTER(c_vp)]),
+    'mec_absmax_f32': (c_int, [c_vp, ctypes.c_longlong, c_fp, c_vp]),
     'mec_precision': (c_int, [c_vp]),
     'mec_destroy': (c_int, [c_vp]),
     'mec_speech_fwd': (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),

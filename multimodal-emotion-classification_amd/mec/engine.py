@@ -80,6 +80,7 @@ class HipModel:
         self._copts = dict(opts or {})  # creation-time knobs (mec_create_opt)
         self._knobs = []                # set_option calls, replayed onto a re-created handle
         self._twin = None
+        self._x3_cal = None             # observed maxima of a calibrated image handle (ImageEncoder.calibrate)
         self.x3_reruns = 0              # batches re-run on the fp32 engine after a range trip
         self._lock = threading.Lock()
         self.handle = None
@@ -93,6 +94,13 @@ class HipModel:
         h = ctypes.c_void_p()
         torch.cuda.set_device(self.device)
         spec = ','.join(f'{k}={int(v)}' for k, v in copts.items()).encode()
+        if self._x3_cal is not None:  # a calibrated fp32x3 handle: the observed maxima set the plane exponents
+            cal = np.ascontiguousarray(self._x3_cal, np.float32)
+            _lib.check(self.lib.mec_create_x3_calibrated(KINDS[self.kind], blob.ctypes.data_as(_lib.c_fp), blob.size,
+                                                         self.device.index, spec, cal.ctypes.data_as(_lib.c_fp),
+                                                         int(cal.size), ctypes.byref(h)),
+                       f'mec_create_x3_calibrated({self.kind})')
+            return h
         _lib.check(self.lib.mec_create_opt(KINDS[self.kind], blob.ctypes.data_as(_lib.c_fp), blob.size,
                                            self.device.index, _lib.PRECISIONS[self.precision], spec, ctypes.byref(h)),
                    f'mec_create({self.kind}, {self.precision})')
@@ -140,11 +148,15 @@ class HipModel:
         return self._twin
 
     def x3_widen(self):
-        """Re-create this fp32x3 handle with X3_HEADROOM_STEP more binades of plane headroom."""
+        """Re-create this fp32x3 handle with X3_HEADROOM_STEP more binades of plane headroom (a calibrated
+        handle keeps its observed bounds: the headroom applies on top of them)."""
         hr = min(24, self.x3_headroom + self.X3_HEADROOM_STEP)
         if hr == self.x3_headroom:
             return
-        copts = dict(self._copts, x3_headroom=hr)
+        self._recreate(dict(self._copts, x3_headroom=hr))
+
+    def _recreate(self, copts):
+        """Replace the handle by one created with `copts` (and the calibration held), the knobs replayed."""
         with self._lock:
             torch.cuda.synchronize(self.device)  # nothing of the old handle may still run
             h = self._create(copts)
@@ -474,6 +486,48 @@ class ImageEncoder(HipModel):
         """arrays: u8 images [H,W,C] of any sizes inside the GPU resize's domain, one C (1 or 3) for all:
         resized on the GPU as PIL resizes them (resize_ragged), then forward_u8."""
         return self.forward_u8(resize_ragged(arrays, self.device))
+
+    def x3_names(self):
+        """The activation tensors with an fp32x3 plane exponent, in x3_report's order (mec_model_x3_names)."""
+        r = self.lib.mec_model_x3_names(self.handle)
+        if r is None:
+            _lib.check(-1, 'mec_model_x3_names')
+        return r.decode().split()
+
+    def calibrate(self, batches):
+        """Set this fp32x3 handle's plane exponents from observed data instead of the BatchNorm estimate.
+        batches: one u8 batch (what `forward` or `forward_u8` takes), or a list of them. They run on the
+        exact-fp32 twin with its observation armed (mec_model_x3_observe): max |x| of every tensor that has
+        an exponent, over all the batches. The handle is then re-created from those maxima
+        (mec_create_x3_calibrated: the same 64x margin to the f16 range, now over what was seen) the way
+        `x3_widen` re-creates it, and keeps them: a later `x3_widen` adds its headroom on top.
+        -> {tensor name: (observed max |x|, exponent s)}. ValueError unless precision is 'fp32x3'."""
+        if self.precision != 'fp32x3':
+            raise ValueError(f"calibrate: an fp32x3 handle's plane exponents are calibrated; this one is {self.precision}")
+        batches = [batches] if isinstance(batches, torch.Tensor) else list(batches)
+        if not batches:
+            raise ValueError('calibrate: no batch to observe')
+        twin = self.fp32_twin()
+        with torch.cuda.device(self.device):
+            n = self.lib.mec_model_x3_observe(twin.handle, 1)
+            if n < 0:
+                _lib.check(n, 'mec_model_x3_observe')
+            try:
+                for x in batches:
+                    twin.forward(x) if x.dim() == 3 else twin.forward_u8(x)
+                seen = np.zeros(n, np.float32)
+                if self.lib.mec_model_x3_observed(twin.handle, seen.ctypes.data_as(_lib.c_fp), n) != n:
+                    _lib.check(-1, 'mec_model_x3_observed')  # (it synchronized the device)
+            finally:
+                self.lib.mec_model_x3_observe(twin.handle, 0)
+        twin.check()
+        names = self.x3_names()
+        if not np.isfinite(seen).all():
+            raise MecError('calibrate: an inf or a NaN in ' + ', '.join(k for k, v in zip(names, seen) if not np.isfinite(v)))
+        self._x3_cal = seen
+        self._recreate(self._copts)
+        s = {ln.split()[0]: int(ln.split()[1][2:]) for ln in self.x3_report().splitlines()[1:]}
+        return {k: (float(v), s[k]) for k, v in zip(names, seen)}
 
 
 def resize_ragged(arrays, device=None, channels: int = 3) -> torch.Tensor:
@@ -988,6 +1042,15 @@ class FusedPipeline:
     def _fuse_mixed(self, plan, s, t, i):
         pair = lambda o, n: (o[0], o[2]) if n else None  # noqa: E731
         return self.fusion.forward_mixed(plan, *(pair(o, n) for o, n in zip((s, t, i), plan.counts)))
+
+    def calibrate_image(self, gray):
+        """`ImageEncoder.calibrate` on the image encoder (fp32x3 pipelines): gray u8 [B,48,48], or a list of
+        such batches. The re-created handle has an empty autotune cache, so the serial first-batch rule starts
+        over: the next batch of every size runs serially again. -> {tensor name: (observed max |x|, s)}."""
+        res = self.image.calibrate(gray)
+        self._tuned.clear()
+        self._tuned_mixed.clear()
+        return res
 
     def wait(self, stream=None):
         """Make `stream` (default: the current one) wait for the last batch's fusion."""
