@@ -562,9 +562,12 @@ int mec_bert_attn(const mec_attn_args* a, void* stream);
  * use). Every pair of settings of one knob gives bit-identical outputs, except "fusion_r" 4 vs
  * 1|2, "conv3x3_halo" 0 vs 1, "gemm_x3_order" 0 vs 1 and "gelu_x3" 0 vs 1 (fp32 reassociation or
  * erf evaluation, all within the oracle tolerance).
- *   "gemm_bn" [0]|id       force one f16 GEMM tile (0 = autotune), "gemm_autotune" 0|[1]
+ *   "gemm_bn" [0]|id       force one f16 GEMM tile (0 = autotune), "gemm_autotune" 0|[1]. The tile ids are
+ *                          defined in one place, the catalogue csrc/gemm_tiles.h (MEC_GEMM_TILES; fp32 engine:
+ *                          MEC_GEMM_F32_TILES); every key below that takes an id accepts 0 and those ids
  *   "gemm_bn_tag" tag*100000+id   force a tile for one launch class (e.g. 3 = BERT O-proj)
- *   "gemm_f32_tile" [0]|1..8  force one fp32 GEMM tile (0 = autotune; 5..8 = 1..4 on 16x16x4)
+ *   "gemm_f32_tile" [0]|1..8  force one fp32 GEMM tile (0 = autotune; 5..8 = 1..4 on 16x16x4; the fp32
+ *                          catalogue's ids)
  *   "gemm_f32_tag" tag*100000+id  pin an fp32 tile for one launch class (default: BERT FFN1 -> 8)
  *   "gemm_f32_family" 0|[16]|32  fp32 tiles of one MFMA shape only (16x16x4 / 32x32x2): one k order
  *                          for every shape, so rows do not depend on the batch size
@@ -574,7 +577,8 @@ int mec_bert_attn(const mec_attn_args* a, void* stream);
  *   "gemm_glds_group_m" 0|2|4|[8]|16  the same tile order for the multi-stage GEMM engine
  *   "gemm_x3_order" 0|[1]  split-f16 (fp32x3) GEMM term order: 0 = pass-major (K for lo.hi, then
  *                          hi.lo, then hi.hi), 1 = K-interleaved (each 32-deep k chunk's three terms
- *                          back to back, 16x16x32 tiles 70256 / 70128 / 71128 / 71064 / 70064 / 72128 only);
+ *                          back to back; the catalogue's interleaved-split tiles only, today 70256 / 70128 /
+ *                          71128 / 71064 / 70064 / 72128);
  *                          both fp32-accurate, not the same bits
  *   "gemm_x3_tag" tag*100000+id  pin an interleaved split tile (7xxxx; 0 = autotune) for one launch
  *                          class (FusedPipeline pins BERT FFN2 to 70256 at fp32x3); a pin applies where

@@ -7,6 +7,7 @@
 #include <exception>
 #include <new>
 
+#include "gemm_tiles.h"
 #include "models.h"
 
 namespace mec {
@@ -646,8 +647,9 @@ int set_option(Options& o, const std::string& k, int value) {
   if (k == "speech_spin_limit" && (value == -1 || (probe && value >= 0))) { o.speech_spin_limit = value; return 0; }
   if (k == "gemm_debug" && (value == 0 || (probe && value >= 1 && value <= 6))) { o.gemm_debug = value; return 0; }
   if (k == "gemm_autotune" && (value == 0 || value == 1)) { o.gemm_autotune = value; return 0; }
-  if (k == "gemm_f32_tile" && value >= 0 && value <= 8) { o.gemm_f32_tile = value; return 0; }
-  if (k == "gemm_f32_tag" && value >= 0 && value / 100000 > 0 && value / 100000 < TAG_COUNT && value % 100000 <= 8) {
+  auto f32_tile_ok = [](int id) { return id == 0 || f32_tile(id); };  // 0 = autotune, else a catalogued tile
+  if (k == "gemm_f32_tile" && f32_tile_ok(value)) { o.gemm_f32_tile = value; return 0; }
+  if (k == "gemm_f32_tag" && value >= 0 && value / 100000 > 0 && value / 100000 < TAG_COUNT && f32_tile_ok(value % 100000)) {
     o.gemm_f32_tag[value / 100000] = value % 100000;
     return 0;
   }
@@ -694,13 +696,7 @@ int set_option(Options& o, const std::string& k, int value) {
     o.audio_debug = value;
     return 0;
   }
-  auto tile_ok = [](int id) {
-    const int v = id % 10000;
-    const bool deep = id == 20256 || id == 30256 || id == 20128 || id == 40256 || id == 41256 || id == 50128 ||
-                      id == 60128 || id == 50256 || id == 70256 || id == 70128 || id == 71128 || id == 71064 ||
-                      id == 70064 || id == 72128;
-    return id == 0 || deep || (id < 20000 && (v == 64 || v == 128 || v == 256 || v == 1064 || v == 1128));
-  };
+  auto tile_ok = [](int id) { return id == 0 || gemm_tile(id); };  // 0 = autotune, else a catalogued tile (gemm_tiles.h)
   if (k == "gemm_bn" && tile_ok(value)) {
     o.gemm_bn = value;
     return 0;
@@ -711,7 +707,7 @@ int set_option(Options& o, const std::string& k, int value) {
     return 0;
   }
   if (k == "gemm_x3_tag" && value >= 0 && value / 100000 > 0 && value / 100000 < TAG_COUNT &&
-      (value % 100000 == 0 || (value % 100000 >= 70000 && tile_ok(value % 100000)))) {
+      (value % 100000 == 0 || gemm_tile_x3i(value % 100000))) {
     o.gemm_x3_tag[value / 100000] = value % 100000;
     return 0;
   }

@@ -7,7 +7,7 @@
 //            never straddles two filter taps
 //   A_DUAL   [A | A2] concatenated along K (a bottleneck's conv3 + its downsample)
 // B is the weight matrix [N,K] (K contiguous = torch Linear layout).
-#include "mec_common.h"
+#include "gemm_tiles.h"
 
 namespace mec {
 
@@ -85,7 +85,7 @@ int launch_gemm(const GemmParams& p0, hipStream_t s, Prof* prof, int tag) {
     // 537 us against 456 planar), while the 256 x 256 ring gains (442 against 465): profiles/r07_x3_paired_gemm.txt
     if (pin == 72128 && p.a_pair) pin = 70256;
     if (pin) {
-      const int bm = (pin / 1000) % 10 == 1 ? 128 : 256, bn = pin % 1000;
+      const int bm = gemm_tile(pin)->bm, bn = gemm_tile(pin)->bn;  // (set_option admits catalogued pins only)
       // the one-stage 72128 tile pays off only with two workgroups on every CU (BERT B = 256: 768 tiles); at
       // B = 128 (384 tiles, BASELINE configs[2]) it ran the text encoder at 8.81 ms against 8.45 autotuned
       // (profiles/r06s_ab_ffn2pin_text_b128.txt)

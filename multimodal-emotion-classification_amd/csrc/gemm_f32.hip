@@ -23,6 +23,7 @@
 #include <mutex>
 
 #include "gemm_common.h"
+#include "gemm_tiles.h"
 
 namespace mec {
 
@@ -224,13 +225,6 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4) ? 2 : 1) void gemm_f32
   gemm_epilogue<BM, BN, WM, WN, MF>(p, acc, reinterpret_cast<f16*>(smem), m0, n0, wm, wn, wave, lane);
 }
 
-// Tiles (id): 1 = 256 x 128 on 8 waves (2 stages, 96 KB), 2 = 128 x 128 on 4 waves (2 stages,
-// 64 KB: two blocks per CU), 3 = 128 x 64 on 4 waves (3 stages), 4 = 256 x 256 on 8 waves
-// (wave tile 128 x 64, 2 stages, 128 KB), all on the 32x32x2 MFMA; 5..8 = the same tiles on
-// the 16x16x4 MFMA. Tiles of one MFMA shape accumulate each output along the same k order
-// (bit-identical); the two shapes sum in different orders (rounding-level difference).
-static int tile_n(int id) { const int b = (id - 1) % 4 + 1; return b == 3 ? 64 : (b == 4 ? 256 : 128); }
-
 template <int BM, int BN, int WM, int WN, int NS, int MF = 32>
 static int launch_f32(const GemmParams& p0, hipStream_t s) {
   GemmParams p = p0;
@@ -245,67 +239,36 @@ static int launch_f32(const GemmParams& p0, hipStream_t s) {
   return 0;
 }
 
+// One case per catalogue line (gemm_tiles.h).
 static int launch_tile(const GemmParams& p, hipStream_t s, int id) {
   switch (id) {
-    case 1: return launch_f32<256, 128, 4, 2, 2>(p, s);
-    case 2: return launch_f32<128, 128, 2, 2, 2>(p, s);
-    case 3: return launch_f32<128, 64, 2, 2, 3>(p, s);
-    case 4: return launch_f32<256, 256, 2, 4, 2>(p, s);
-    case 5: return launch_f32<256, 128, 4, 2, 2, 16>(p, s);
-    case 6: return launch_f32<128, 128, 2, 2, 2, 16>(p, s);
-    case 7: return launch_f32<128, 64, 2, 2, 3, 16>(p, s);
-    case 8: return launch_f32<256, 256, 2, 4, 2, 16>(p, s);
+#define MEC_TILE_CASE(ID, BM, BN, WM, WN, NS, MF) \
+  case ID: return launch_f32<BM, BN, WM, WN, NS, MF>(p, s);
+    MEC_GEMM_F32_TILES(MEC_TILE_CASE)
+#undef MEC_TILE_CASE
     default: set_error("gemm_f32: unsupported tile id"); return -1;
   }
 }
 
-// Cache key: engine 1 (this engine) + the shape, in the calling handle's tune_cache().
-// engine slot: 1 + the MFMA family allowed when the shape was tuned, so changing
+// Cache key: this engine's slot + the shape, in the calling handle's tune_cache().
+// engine slot: ENGINE_F32 + the MFMA family allowed when the shape was tuned, so changing
 // gemm_f32_family on a handle never reuses a tile of the other family (other k order)
-static int f32_engine() { return 1 + opt().gemm_f32_family; }
+static int f32_engine() { return ENGINE_F32 + opt().gemm_f32_family; }
 
 static std::array<int, 11> f32_key(const GemmParams& p) {
   return {f32_engine(), p.amode, p.M, p.N, p.K, p.H, p.W, p.C, p.ks, p.stride, p.pad};
 }
 
-// MFMA family allowed by opt().gemm_f32_family (0: both; 16: ids 5..8 on 16x16x4; 32: ids 1..4
-// on 32x32x2). The two families sum in different k orders, so one family for every shape makes
-// a row's result independent of the batch size (the tuned tile may change with M, its bits not).
-static bool family_ok(int id) {
-  const int fam = opt().gemm_f32_family;
-  return fam == 0 || (fam == 16 ? id >= 5 : id <= 4);
+// Whether tile t fits N and the MFMA family allowed by opt().gemm_f32_family (0: both; 16: the 16x16x4
+// tiles; 32: the 32x32x2 tiles). The two families sum in different k orders, so one family for every shape
+// makes a row's result independent of the batch size (the tuned tile may change with M, its bits not).
+static bool tile_fits(const GemmF32Tile* t, const GemmParams& p, bool any_family = false) {
+  return t && p.N % t->bn == 0 && (any_family || !opt().gemm_f32_family || t->mf == opt().gemm_f32_family);
 }
 
 static int heuristic_tile(const GemmParams& p) {
   const int id = (p.N % 128) ? 3 : ((long)((p.M + 255) / 256) * (p.N / 128) >= 512 ? 1 : 2);
   return opt().gemm_f32_family == 16 ? id + 4 : id;
-}
-
-// First launch of a shape: time every legal tile (median of 3 launches, hipEvents on the
-// caller's stream; skipped while the stream is being captured) and keep the fastest.
-static int tune_tile(const GemmParams& p, hipStream_t s, int* out) {
-  constexpr int REPS = 3;
-  hipEvent_t ev[REPS + 1];
-  for (auto& e : ev) MEC_HIP(hipEventCreate(&e));
-  float best = 1e30f;
-  int best_id = heuristic_tile(p);
-  for (int id = 1; id <= 8; ++id) {
-    if (p.N % tile_n(id) || !family_ok(id)) continue;
-    MEC_TRY(launch_tile(p, s, id));
-    MEC_HIP(hipEventRecord(ev[0], s));
-    for (int r = 0; r < REPS; ++r) {
-      MEC_TRY(launch_tile(p, s, id));
-      MEC_HIP(hipEventRecord(ev[r + 1], s));
-    }
-    MEC_HIP(hipEventSynchronize(ev[REPS]));
-    float t[REPS];
-    for (int r = 0; r < REPS; ++r) MEC_HIP(hipEventElapsedTime(&t[r], ev[r], ev[r + 1]));
-    std::sort(t, t + REPS);
-    if (t[REPS / 2] < best) { best = t[REPS / 2]; best_id = id; }
-  }
-  for (auto& e : ev) (void)hipEventDestroy(e);
-  *out = best_id;
-  return 0;
 }
 
 int gemm_f32_tuned(int amode, int M, int N, int K) { return tune_cache().find_shape(f32_engine(), amode, M, N, K); }
@@ -326,31 +289,32 @@ int launch_gemm_f32(const GemmParams& p, hipStream_t s, Prof* prof, int tag) {
   }
   const auto key = f32_key(p);
   int id = opt().gemm_f32_tile;
-  if (!id && tag > 0 && tag < TAG_COUNT && opt().gemm_f32_tag[tag] && p.N % tile_n(opt().gemm_f32_tag[tag]) == 0 &&
-      family_ok(opt().gemm_f32_tag[tag])) {
+  if (!id && tag > 0 && tag < TAG_COUNT && tile_fits(f32_tile(opt().gemm_f32_tag[tag]), p)) {
     id = opt().gemm_f32_tag[tag];
     tune_cache().put(key, id);  // so mec_model_gemm_query reports the tile that runs
   }
   if (id) {
-    MEC_REQUIRE(id >= 1 && id <= 8 && p.N % tile_n(id) == 0, "gemm_f32: forced tile does not fit N");
+    MEC_REQUIRE(tile_fits(f32_tile(id), p, /*any_family=*/true), "gemm_f32: forced tile does not fit N");
   } else {
     id = tune_cache().find(key);
   }
   if (!id) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    const bool capturing = !(hipStreamIsCapturing(s, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone);
-    if (opt().gemm_autotune && !capturing) {
-      MEC_TRY(tune_tile(p, s, &id));
-    } else {
-      id = heuristic_tile(p);
-    }
     // inside capture the heuristic tile is untimed: not cached while the autotune family is held to one
     // MFMA shape (gemm_f32_family 16 / 32: every tile sums in one k order, same bits), so the first
     // eager launch still tunes; cached with both families allowed, so replay and eager bits agree
-    if (!capturing || !opt().gemm_f32_family) tune_cache().put(key, id);
-    if (getenv("MEC_GEMM_TRACE"))
-      fprintf(stderr, "MEC_GEMM_F32 amode=%d M=%d N=%d K=%d H=%d C=%d ks=%d stride=%d act=%d R=%d tile=%d\n", p.amode,
-              p.M, p.N, p.K, p.H, p.C, p.ks, p.stride, p.act, p.R != nullptr, id);
+    MEC_TRY(first_launch_tile(
+        key, s, !opt().gemm_f32_family,
+        [&](int* out) {  // the median of 3 launches of every tile that fits
+          return tune_tiles<3>(
+              kGemmF32Tiles, [&](const GemmF32Tile& t) { return tile_fits(&t, p); },
+              [&](int t) { return launch_tile(p, s, t); }, s, heuristic_tile(p), out);
+        },
+        [&] { return heuristic_tile(p); },
+        [&](int t) {
+          fprintf(stderr, "MEC_GEMM_F32 amode=%d M=%d N=%d K=%d H=%d C=%d ks=%d stride=%d act=%d R=%d tile=%d\n", p.amode,
+                  p.M, p.N, p.K, p.H, p.C, p.ks, p.stride, p.act, p.R != nullptr, t);
+        },
+        &id));
   }
   if (prof) MEC_TRY(prof->begin(tag, s));
   MEC_TRY(launch_tile(p, s, id));

@@ -216,6 +216,16 @@ struct Options {
 
 constexpr long kX3PinMinTiles = 128;  // gemm_x3_tag pins apply from this many tiles (half of 256 CUs)
 
+// Engine slot of a tune-cache key: which engine tuned the shape, and on which operands. The fp32 engine
+// adds the MFMA family its tiles were held to (ENGINE_F32 + gemm_f32_family: 1, 17, 33).
+enum TuneEngine {
+  ENGINE_F16 = 0,         // gemm_glds.hip, f16 operands
+  ENGINE_F32 = 1,         // gemm_f32.hip (+ family)
+  ENGINE_X3_PASS = 2,     // gemm_glds.hip, split operands, pass-major terms (gemm_x3_order 0)
+  ENGINE_X3I = 3,         // gemm_glds.hip, split operands, K-interleaved terms
+  ENGINE_X3I_PAIRED = 4,  // the same on paired hi / lo planes
+};
+
 // GEMM autotuner results: tile id per (engine, shape), per handle.
 struct TuneCache {
   std::map<std::array<int, 11>, int> m;
