@@ -353,6 +353,39 @@ int mec_fusion_fwd_mixed(mec_model* m, const mec_fusion_mixed_args* a, void* str
  *   zero_crossing_rate / spectral_centroid / spectral_rolloff / rms). */
 int mec_audio_fwd(mec_model* m, const float* wave, int B, int n_samples, float* feat, float* tuning, void* stream);
 
+/* Decode and resample a ragged batch of PCM clips into the waveforms mec_audio_fwd takes (csrc/audio_load.hip;
+ * MEC_AUDIO handle, whose blob gives the target rate sr). What load_audio does per file on the host,
+ *   librosa.load(path, sr=22050, duration=3) + pad/trim   preprocessing/audio_preprocessing.py:12-19
+ * for audio that is already PCM: decode to float32 as libsndfile normalises it (U8 (x - 128) / 128, S16 x / 2^15,
+ * S24 x / 2^23, S32 (float)x * 2^-31, F32 as stored), mean of two channels in float32, resample, and zeros up to
+ * n_out or a cut at it. Clip i gives min(n_out, ceil(frames_i * (sr / rate_i))) samples (float64, as librosa
+ * 0.10.0 resample computes it). A clip at the rate sr is copied: bit for bit the host's waveform.
+ *
+ * The resampler is this library's own (csrc/resample_design.h): a polyphase Kaiser-windowed sinc, passband to
+ * 0.913 of the lower Nyquist, 125 dB design attenuation, float64 taps and accumulation and one rounding to
+ * float32. It is held to that float64 definition; parity with librosa's soxr_hq is NOT pinned.
+ *
+ * mec_resample_on_gpu: 1 when rate_in -> rate_out is in the domain: both in 1 .. 192000, max(up, down) <= 8192
+ * for the reduced ratio up / down, at most 2^21 taps, and one output cycle's input window within LDS (always so
+ * for rate_out = 22050). mec_resample_plan: up, down and half (taps = 2 * half + 1; half = 0 is the identity
+ * plan, rate_in == rate_out). mec_resample_taps: the n = 2 * half + 1 taps, unit sum. These three need no GPU.
+ *
+ * mec_audio_load_ragged: clip i is little-endian interleaved frames at byte offs[i] of the device buffer src
+ * (src_bytes long), any byte alignment; desc (HOST, [B, 4]) = fmt, channels (1 or 2), rate, frames. wave: device
+ * f32 [B, n_out]. Everything is checked on the host before any launch ("requirement failed:
+ * mec_audio_load_ragged: clip <i> ..."). B == 0 returns 0 without a launch; frames == 0 gives a zero row. Tap
+ * tables are built per rate on first use and cached on the handle (16 at most, least recently used dropped; a
+ * call may name at most 16 distinct rates). Asynchronous on `stream`; not graph-capturable.
+ * mec_audio_load_prof_*: hipEvent timing of the kernel, process-wide, as mec_resize_prof_*. */
+enum { MEC_PCM_U8 = 0, MEC_PCM_S16 = 1, MEC_PCM_S24 = 2, MEC_PCM_S32 = 3, MEC_PCM_F32 = 4 };
+int mec_resample_on_gpu(int rate_in, int rate_out);
+int mec_resample_plan(int rate_in, int rate_out, int* up, int* down, int* half);
+int mec_resample_taps(int rate_in, int rate_out, double* h, size_t n);
+int mec_audio_load_ragged(mec_model* m, const uint8_t* src, const int64_t* offs, const int32_t* desc, int B,
+                          size_t src_bytes, float* wave, int n_out, void* stream);
+int mec_audio_load_prof_enable(int on);
+int mec_audio_load_prof_read(double* ms, int* count);
+
 /* Weighted-average fallback (float64, like numpy); any of s/t/i may be NULL (= zeros).
  * Replaces MultimodalFusion.fuse_predictions  inference/multimodal_fusion.py:184-199. */
 int mec_fuse_weighted(const float* s_probs, const float* t_probs, const float* i_probs, int B,

@@ -407,6 +407,15 @@ int mec_audio_fwd(mec_model* m, const float* wave, int B, int n_samples, float* 
   })
 }
 
+int mec_audio_load_ragged(mec_model* m, const uint8_t* src, const int64_t* offs, const int32_t* desc, int B,
+                          size_t src_bytes, float* wave, int n_out, void* stream) {
+  API_GUARD({
+    auto* p = as<AudioModel>(m, KIND_AUDIO);
+    if (!p) return -1;
+    return p->load_ragged(src, offs, desc, B, src_bytes, wave, n_out, S(stream));
+  })
+}
+
 // First-fit decreasing over 128-slot rows: samples by length descending (ties: ascending index), each into
 // the lowest-numbered row with room, at that row's fill; a new row when none has room. Host only.
 int mec_text_pack_plan(const int32_t* lens, int B, int32_t* row, int32_t* off) {

@@ -84,6 +84,7 @@ enum KernelTag : int {
   TAG_RESIZE_V = 21,
   TAG_CANON_GRAY = 22,  // image_canon.hip: the gray test and the conversion (mec_image_canon_prof_*)
   TAG_CANON_PIX = 23,
+  TAG_AUDIO_LOAD = 24,  // audio_load.hip: decode + resample (mec_audio_load_prof_*)
 };
 
 // Tuning knobs (mec_set_option / mec_model_set_option, include/mec.h). Every model handle

@@ -3,7 +3,11 @@
 // stream. One handle is used by one host thread at a time (the Python wrapper locks).
 #pragma once
 #include "../../include/mec.h"
+#include <list>
+
 #include "mec_common.h"
+#include "ragged_stage.h"
+#include "resample_design.h"
 
 namespace mec {
 
@@ -71,6 +75,16 @@ struct SpeechModel : Model {
 // ---------------------------------------------------------------- speech features (audio.hip)
 // blob = [sample_rate, n_fft, hop, n_mels, n_mfcc] (config.py:57-59 + librosa defaults); the
 // handle owns the filterbank / window / twiddle tables and a grow-only workspace.
+// One cached tap table of the audio front end (audio_load.hip): rate_in -> the handle's rate, phase-major on
+// the device; `last` is recorded after every call that read it.
+struct ResampleTable {
+  int rate_in = 0;
+  rs::Plan plan;
+  double* dev = nullptr;
+  hipEvent_t last = nullptr;
+  uint64_t stamp = 0;
+};
+
 struct AudioModel : Model {
   int sr = 22050, n_mfcc = 40, lo_bin = 0, hi_bin = 0, mel_nnz = 0, mel_ch = 0;
   DevBuf tables, ws;
@@ -79,6 +93,16 @@ struct AudioModel : Model {
   int create(const float* blob, size_t n);
   // wave f32 [B, L] -> feat f32 [B, n_mfcc + 16]; tuning f32 [B] (estimate_tuning) or null
   int forward(const float* wave, int B, int L, float* feat, float* tuning, hipStream_t s);
+  // mec_audio_load_ragged (audio_load.hip): the descriptors' staging and the tap tables, under load_mu
+  static constexpr int kMaxTables = 16;
+  std::mutex load_mu;
+  StageBuf load_stage;
+  std::list<ResampleTable> load_tabs;
+  uint64_t load_stamp = 0;
+  ~AudioModel() override;
+  int load_table(int rate_in, const std::vector<int>& keep, ResampleTable** out);
+  int load_ragged(const uint8_t* src, const int64_t* offs, const int32_t* desc, int B, size_t src_bytes, float* wave,
+                  int n_out, hipStream_t s);
 };
 
 // ---------------------------------------------------------------- fusion model

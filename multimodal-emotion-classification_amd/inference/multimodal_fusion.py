@@ -34,12 +34,12 @@ _MODS = ('speech', 'text', 'image')
 
 class MultimodalFusion:
     def __init__(self, weights=None, seed=None, device=None, precision=None, image_resize='host',
-                 image_convert='host'):
+                 image_convert='host', audio_load='host'):
         weights = weights or {}
         self.emotions = Config.EMOTIONS
         self.weights = [0.3, 0.35, 0.35]  # speech, text, image (reference :23)
         self.fusion_model = None
-        self.speech_inference = SpeechInference(weights.get('speech'), seed, device)
+        self.speech_inference = SpeechInference(weights.get('speech'), seed, device, load=audio_load)
         self.text_inference = TextInference(weights.get('text'), seed, device, precision=precision)
         self.image_inference = ImageInference(weights.get('image'), seed, device, precision=precision,
                                               resize=image_resize, convert=image_convert)
@@ -163,23 +163,19 @@ class MultimodalFusion:
             reqs.append((a or None, t or None, i or None))
         present = np.array([[x is not None for x in r] for r in reqs], bool).reshape(-1, 3)
         # ---- host: decode every file first
-        ap = _speech._preprocessing() if present[:, 0].any() else None
-        waves, wave_at, hostf, hostf_at = [], [], [], []  # compact speech rows: GPU features / host features
+        # (audio_load='gpu': a PCM WAV file's bytes are read here and decoded on the GPU below; any other file
+        # is decoded here, per file)
+        audio = self.speech_inference.file_batch(bool(present[:, 0].any()))
         images = []  # per compact image row: what ImageInference.route makes of the image
-        ns = ni = 0
+        ni = 0
         for b, (a, _, i) in enumerate(reqs):
             if a is not None:
                 try:
-                    audio, sr = ap.load_audio(a)
-                    if int(sr) != Config.SAMPLE_RATE:  # as SpeechInference._file_features
-                        hostf.append(np.asarray(ap.preprocess_audio(a), np.float32).reshape(56))
-                        hostf_at.append(ns)
-                    else:
-                        waves.append(np.asarray(audio, np.float32).reshape(-1))
-                        wave_at.append(ns)
+                    audio.add(a)
+                except _speech.PreprocessingMissing:  # as today: not a property of the request
+                    raise
                 except Exception as e:
                     raise ValueError(f'request {b}: cannot read audio {a!r}: {e}') from e
-                ns += 1
             if i is not None:
                 try:
                     from PIL import Image
@@ -190,16 +186,10 @@ class MultimodalFusion:
                 ni += 1
         texts = [t for _, t, _ in reqs if t is not None]
         dev = self.device
-        at_dev = lambda at: torch.tensor(at, dtype=torch.int64, device=dev)  # noqa: E731
         # ---- encoders, each over its compact rows
         speech = text = image = None
-        if ns:
-            x = torch.empty((ns, 56), dtype=torch.float32, device=dev)
-            if waves:
-                x.index_copy_(0, at_dev(wave_at),
-                              self.speech_inference.features_from_waveforms(engine.to_device(np.stack(waves), dev)))
-            if hostf:
-                x.index_copy_(0, at_dev(hostf_at), engine.to_device(np.stack(hostf), dev))
+        if audio.n:
+            x = audio.features()
             sf, _, sp = self.speech_inference.model.forward(x)
             speech = (sf, sp)
         if texts:

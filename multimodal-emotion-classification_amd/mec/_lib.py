@@ -101,6 +101,12 @@ SIGNATURES = {
     'mec_tok_encode': (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     'mec_tok_destroy': (c_int, [c_vp]),
     'mec_audio_fwd': (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp]),
+    'mec_resample_on_gpu': (c_int, [c_int, c_int]),
+    'mec_resample_plan': (c_int, [c_int, c_int] + [ctypes.POINTER(c_int)] * 3),
+    'mec_resample_taps': (c_int, [c_int, c_int, c_vp, ctypes.c_size_t]),
+    'mec_audio_load_ragged': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, ctypes.c_size_t, c_vp, c_int, c_vp]),
+    'mec_audio_load_prof_enable': (c_int, [c_int]),
+    'mec_audio_load_prof_read': (c_int, [c_dp, ctypes.POINTER(c_int)]),
     'mec_fuse_weighted': (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_vp]),
     'mec_fuse_weighted_f64': (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_vp]),
     'mec_resize_u8': (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp]),

@@ -13,7 +13,7 @@ import threading
 import numpy as np
 import torch
 
-from . import _lib, image as _image, synthetic, tokenize as _tok
+from . import _lib, image as _image, synthetic, tokenize as _tok, wav as _wav
 from ._lib import MecError
 
 TAG_BERT_FFN2 = 5  # launch class of BERT's FFN2 GEMM (mec_common.h Tag)
@@ -710,6 +710,63 @@ class AudioFeaturizer(HipModel):
             _lib.check(self.lib.mec_audio_fwd(self.handle, _ptr(wave), B, n, _ptr(feat), _ptr(tun),
                                               _stream(self.device)), 'mec_audio_fwd')
         return (feat, tun) if return_tuning else feat
+
+
+class AudioLoader:
+    """load_audio on the GPU for PCM clips (mec_audio_load_ragged; csrc/audio_load.hip): a ragged batch of
+    (bytes, fmt, channels, rate, frames) clips, as mec.wav.read_clip gives them, is packed into one pinned
+    staging buffer, uploaded in one copy, and decoded, mixed to mono, resampled to the featurizer's rate and
+    padded or trimmed to n_out = 3 s on the device -> f32 [B, n_out], what AudioFeaturizer.forward takes.
+    It shares the featurizer's handle (the tap tables are cached there). Asynchronous on the current stream."""
+
+    def __init__(self, featurizer: 'AudioFeaturizer', n_out: int | None = None):
+        self.audio = featurizer
+        self.device = featurizer.device
+        self.sample_rate = featurizer.sample_rate
+        self.n_out = int(n_out) if n_out is not None else 3 * featurizer.sample_rate
+
+    def load(self, clips) -> torch.Tensor:
+        clips = list(clips)
+        B, dev = len(clips), self.device
+        views = [np.frombuffer(c[0], np.uint8) for c in clips]
+        desc = np.array([c[1:5] for c in clips], np.int32).reshape(-1, 4)
+        offs, _, total = _image.pack_layout([v.size for v in views])
+        with torch.cuda.device(dev):
+            wave = torch.empty((B, self.n_out), dtype=torch.float32, device=dev)
+            if B:
+                src = _pinned(total, zip(offs, views)).to(dev, non_blocking=True) if total else None
+                with self.audio._lock:
+                    _lib.check(self.audio.lib.mec_audio_load_ragged(
+                        self.audio.handle, _ptr(src), offs.ctypes.data, desc.ctypes.data, B, total, _ptr(wave),
+                        self.n_out, _stream(dev)), 'mec_audio_load_ragged')
+        return wave
+
+    def read_one(self, path):
+        """mec.wav.read_clip for this loader's rate and length: the clip, or None for a file it declines."""
+        return _wav.read_clip(path, self.sample_rate, self.n_out / self.sample_rate)
+
+    def read(self, paths):
+        """-> (clips, at, declined): the clips of the files mec.wav.read_clip takes, their positions in
+        `paths`, and the positions of the files it declines (for the host loader)."""
+        clips, at, declined = [], [], []
+        for i, p in enumerate(paths):
+            c = self.read_one(p)
+            (declined if c is None else at).append(i)
+            if c is not None:
+                clips.append(c)
+        return clips, at, declined
+
+
+def audio_load_prof(on: bool):
+    """hipEvent timing of the audio front end's kernel (mec_audio_load_prof_enable), process-wide."""
+    _lib.check(_lib.load().mec_audio_load_prof_enable(1 if on else 0), 'mec_audio_load_prof_enable')
+
+
+def audio_load_prof_read():
+    """(kernel ms, calls) since the last read or enable; synchronizes on the events."""
+    ms, n = ctypes.c_double(), ctypes.c_int()
+    _lib.check(_lib.load().mec_audio_load_prof_read(ctypes.byref(ms), ctypes.byref(n)), 'mec_audio_load_prof_read')
+    return ms.value, n.value
 
 
 class FusionHead(HipModel):
