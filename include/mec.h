@@ -481,6 +481,16 @@ int mec_gemm_f16x3(const void* A, long long a_lo, const void* B, long long b_lo,
  * c_lo apart as above. Same values as mec_gemm_f16x3 bit for bit (K-interleaved term order only). */
 int mec_gemm_f16x3_paired(const void* A, const void* B, float oscale, const float* bias, const float* R, void* C16,
                           int c_paired, long long c_lo, float* C32, int M, int N, int K, int act, void* stream);
+/* mec_gemm_f16x3_paired with the two epilogue inputs it lacks, as mec_gemm_ex names them: r_stats [M][2] =
+ * (mean, rstd) with r_gamma, r_beta [N] (all three or none; needs R): the f32 R enters as
+ * fma((R - mean) * rstd, gamma, beta), the deferred LayerNorm of BERT's O-projection and FFN2; cscale (1 =
+ * none) multiplies the value that the C16 planes carry. act as mec_gemm_ex. range_flag: a device word that
+ * the kernel sets to 1 when a C16 plane value leaves the f16 range (NULL: the calling handle's flag, none for
+ * a handle-less call); it is never cleared here. */
+int mec_gemm_f16x3_paired_ln(const void* A, const void* B, float oscale, const float* bias, const float* R,
+                             const float* r_stats, const float* r_gamma, const float* r_beta, void* C16, int c_paired,
+                             long long c_lo, float cscale, float* C32, int M, int N, int K, int act,
+                             unsigned* range_flag, void* stream);
 int mec_gemm_f16(const void* A, const void* B, const float* bias, const void* R, int r_is_f32, void* C16,
                  float* C32, int M, int N, int K, int act, void* stream);
 /* Implicit-GEMM conv on NHWC f16: x[n,H,W,C], w[Cout][ks][ks][C], y[n,OH,OW,Cout]. */
@@ -646,6 +656,13 @@ int mec_bert_attn(const mec_attn_args* a, void* stream);
  *                          shape (fewer LDS bank conflicts on the depthwise reads) or unswizzled; same bits
  *   "qkv_x3_late_dma" [0]|1|2  fp32x3 fused QKV + attention: every other 256-block of workgroups issues its
  *                          stage refill after its first / second MFMA term group (measured neutral); same bits
+ *   "gemm_x3_pp" 0|[1]|2   fp32x3 split GEMM, tile 70256 on paired planes (BERT's FFN1, FFN2, O-projection and
+ *                          last-layer K|V under x3_layout 1): the four-phase ping-pong schedule with two K
+ *                          tiles in flight instead of the two-stage ring. 0 = ring, 1 = ping-pong for the
+ *                          launches without an activation (FFN2, O-projection, K|V: faster by the median
+ *                          at B = 256; FFN1 measured slower on it and keeps the ring),
+ *                          2 = ping-pong for every launch (tests, A/B). Any batch size; same bits. Planar
+ *                          operands and every other tile run the ring either way
  *   "x3_plane_scale" 0|[1] fp32x3 activation-plane scales, creation-time (mec_create_opt, or the process
  *                          default before mec_create_ex; mec_model_set_option rejects it): 1 = per-tensor
  *                          power-of-two exponents (the envelope above), 0 = unscaled planes (A/B only:

@@ -501,16 +501,38 @@ int mec_gemm_f16x3(const void* A, long long a_lo, const void* B, long long b_lo,
   })
 }
 
+// The paired-operand split GEMM behind both C entries below.
+static int gemm_f16x3_paired(const void* A, const void* B, float oscale, const float* bias, const float* R,
+                             const float* r_stats, const float* r_gamma, const float* r_beta, void* C16, int c_paired,
+                             long long c_lo, float cscale, float* C32, int M, int N, int K, int act, unsigned* flag,
+                             void* stream) {
+  GemmParams g;
+  g.split = 1; g.a_pair = g.b_pair = 1; g.A = A; g.B = reinterpret_cast<const f16*>(B); g.oscale = oscale;
+  g.bias = bias; g.R = R; g.r_f32 = R != nullptr;
+  g.r_stats = reinterpret_cast<const float2*>(r_stats); g.r_g = r_gamma; g.r_b = r_beta;
+  g.C16 = reinterpret_cast<f16*>(C16); g.c_pair = C16 && c_paired; g.c_lo = C16 && !c_paired ? c_lo : 0;
+  g.cscale = cscale; g.C32 = C32; g.M = M; g.N = N; g.K = K; g.act = act; g.ovf = flag;
+  return launch_gemm(g, S(stream), nullptr, TAG_NONE);
+}
+
 int mec_gemm_f16x3_paired(const void* A, const void* B, float oscale, const float* bias, const float* R, void* C16,
                           int c_paired, long long c_lo, float* C32, int M, int N, int K, int act, void* stream) {
   API_GUARD({
     MEC_REQUIRE(!C16 || c_paired || c_lo != 0, "mec_gemm_f16x3_paired: a planar C16 needs c_lo");
-    GemmParams g;
-    g.split = 1; g.a_pair = g.b_pair = 1; g.A = A; g.B = reinterpret_cast<const f16*>(B); g.oscale = oscale;
-    g.bias = bias; g.R = R; g.r_f32 = R != nullptr; g.C16 = reinterpret_cast<f16*>(C16);
-    g.c_pair = C16 && c_paired; g.c_lo = C16 && !c_paired ? c_lo : 0;
-    g.C32 = C32; g.M = M; g.N = N; g.K = K; g.act = act;
-    return launch_gemm(g, S(stream), nullptr, TAG_NONE);
+    return gemm_f16x3_paired(A, B, oscale, bias, R, nullptr, nullptr, nullptr, C16, c_paired, c_lo, 1.f, C32, M, N, K,
+                             act, nullptr, stream);
+  })
+}
+
+int mec_gemm_f16x3_paired_ln(const void* A, const void* B, float oscale, const float* bias, const float* R,
+                             const float* r_stats, const float* r_gamma, const float* r_beta, void* C16, int c_paired,
+                             long long c_lo, float cscale, float* C32, int M, int N, int K, int act,
+                             unsigned* range_flag, void* stream) {
+  API_GUARD({
+    MEC_REQUIRE(!C16 || c_paired || c_lo != 0, "mec_gemm_f16x3_paired_ln: a planar C16 needs c_lo");
+    MEC_REQUIRE(oscale != 0.f && cscale != 0.f, "mec_gemm_f16x3_paired_ln: oscale and cscale must be set (1 = none)");
+    return gemm_f16x3_paired(A, B, oscale, bias, R, r_stats, r_gamma, r_beta, C16, c_paired, c_lo, cscale, C32, M, N, K,
+                             act, range_flag, stream);
   })
 }
 
@@ -672,6 +694,7 @@ int set_option(Options& o, const std::string& k, int value) {
   if (k == "x3_headroom" && value >= 0 && value <= 24) { o.x3_headroom = value; return 0; }
   if (k == "x3_layout" && (value == 0 || value == 1)) { o.x3_layout = value; return 0; }
   if (k == "qkv_x3_late_dma" && value >= 0 && value <= 2) { o.qkv_x3_late_dma = value; return 0; }
+  if (k == "gemm_x3_pp" && value >= 0 && value <= 2) { o.gemm_x3_pp = value; return 0; }
   if (k == "mbv2_layered" && (value == 0 || (value >= 7 && value <= 17))) { o.mbv2_layered = value; return 0; }
   if (k == "mbv2_layered16" && (value == 0 || (value >= 7 && value <= 17))) { o.mbv2_layered16 = value; return 0; }
   if (k == "conv3x3_direct" && (value == 0 || value == 1)) { o.conv3x3_direct = value; return 0; }

@@ -472,8 +472,13 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4) ? 2 : 1) void gemm_gld
 //     x ^ ((r >> 1) & 7)) is then stored as whole 128-B row segments;
 //   * otherwise (BERT FFN2): (acc + bias) in f32 slabs of 32 rows x 256 B per wave (chunk x of row
 //     r at x ^ (r & 15)); each slab's residual loads are all issued before any is consumed.
+//   * X3 (paired split operands, gemm_pp_kernel SP = 3): every output form of the split engine --
+//     f32 residual (plain or deferred LayerNorm) -> f32 for BERT's O-projection and FFN2, paired or
+//     planar hi / lo planes for FFN1 and K|V -- through the same 32-row f32 slabs, read back with
+//     gemm_epilogue's lane map (8 lanes x 8 features per row, 8 rows per pass): 16-B residual loads
+//     and stores, and a paired row's hi and lo stores of four adjacent lanes fill one 128-B line.
 // NOSTORE (probe builds only): everything computed, (almost) nothing stored.
-template <int BM, bool NOSTORE = false, int ACT = -1>
+template <int BM, bool NOSTORE = false, int ACT = -1, bool X3 = false>
 __device__ __forceinline__ void pp_epilogue(const GemmParams& p, floatx4 (&acc)[BM / 32][4], char* smem, int m0,
                                             int n0, int wm, int wn, int tid, int lane) {
   constexpr int HB = BM / 2;    // rows per wave
@@ -516,6 +521,109 @@ __device__ __forceinline__ void pp_epilogue(const GemmParams& p, floatx4 (&acc)[
     }
   };
   const float os = p.oscale;  // 1 except on split operands: fma(acc, 1, b) == acc + b
+  if constexpr (X3) {
+    static_assert(BM == 256, "paired split operands: the 256-row tile only");
+    // lane -> row (lane >> 3) of each 8-row pass, features 8 (lane & 7)..+7 = slab chunks 2 (lane & 7), + 1
+    const int ech = lane & 7, erow = lane >> 3;
+    const int col0 = cw0 + ech * 8;
+    float lng[8], lnb[8];
+    if (p.r_stats) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { lng[e] = p.r_g[col0 + e]; lnb[e] = p.r_b[col0 + e]; }
+    }
+    bool x3bad = false;  // split output left the f16 range (raised once, after the slabs)
+#pragma unroll
+    for (int sl = 0; sl < HB / 32; ++sl) {
+#pragma unroll
+      for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int jb = 0; jb < 4; ++jb) {
+          const int ia = sl * 2 + a;
+          const float4 v = make_float4(__builtin_fmaf(acc[ia][jb][0], os, bb[jb].x),
+                                       __builtin_fmaf(acc[ia][jb][1], os, bb[jb].y),
+                                       __builtin_fmaf(acc[ia][jb][2], os, bb[jb].z),
+                                       __builtin_fmaf(acc[ia][jb][3], os, bb[jb].w));
+          const int r = a * 16 + l16, x = jb * 4 + q;
+          *reinterpret_cast<float4*>(reg + r * 256 + ((x ^ (r & 15)) << 4)) = v;
+        }
+      float rv[4][8];  // every residual load of the slab is issued before any is consumed
+#pragma unroll
+      for (int ps = 0; ps < 4; ++ps) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) rv[ps][e] = 0.f;
+        if (p.R) {
+          const int rowc = min(rw0 + sl * 32 + ps * 8 + erow, M - 1);
+          const size_t base = (size_t)rowc * N + col0;
+          if (p.r_f32) {
+            const float* R = reinterpret_cast<const float*>(p.R) + base;
+            const float4 r0 = *reinterpret_cast<const float4*>(R);
+            const float4 r1 = *reinterpret_cast<const float4*>(R + 4);
+            rv[ps][0] = r0.x; rv[ps][1] = r0.y; rv[ps][2] = r0.z; rv[ps][3] = r0.w;
+            rv[ps][4] = r1.x; rv[ps][5] = r1.y; rv[ps][6] = r1.z; rv[ps][7] = r1.w;
+            if (p.r_stats) {
+              const float2 st = p.r_stats[rowc];
+#pragma unroll
+              for (int e = 0; e < 8; ++e) rv[ps][e] = __builtin_fmaf((rv[ps][e] - st.x) * st.y, lng[e], lnb[e]);
+            }
+          } else {  // (launch_gemm: paired operands take no split residual)
+            const half8 r8 = *reinterpret_cast<const half8*>(reinterpret_cast<const f16*>(p.R) + base);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) rv[ps][e] = (float)r8[e];
+          }
+        }
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int ps = 0; ps < 4; ++ps) {
+        const int sr = ps * 8 + erow, row = rw0 + sl * 32 + sr;
+        const float4 x0 = *reinterpret_cast<const float4*>(reg + sr * 256 + (((2 * ech) ^ (sr & 15)) << 4));
+        const float4 x1 = *reinterpret_cast<const float4*>(reg + sr * 256 + (((2 * ech + 1) ^ (sr & 15)) << 4));
+        float v[2][4] = {{x0.x + rv[ps][0], x0.y + rv[ps][1], x0.z + rv[ps][2], x0.w + rv[ps][3]},
+                         {x1.x + rv[ps][4], x1.y + rv[ps][5], x1.z + rv[ps][6], x1.w + rv[ps][7]}};
+        act4(v[0]);
+        act4(v[1]);
+        if (row < M && (!NOSTORE || v[0][0] == 1234.5f)) {
+          const size_t base = (size_t)row * N + col0;
+          if (p.C16 && (p.c_lo || p.c_pair)) {  // split output: planes of v * cscale, the lo plane carries the rest
+            float u[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) u[e] = v[e >> 2][e & 3];
+            if (p.cscale != 1.f) {  // (a uniform branch: most split outputs carry their scale in the bias)
+#pragma unroll
+              for (int e = 0; e < 8; ++e) u[e] *= p.cscale;
+            }
+            half8 h, l;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+              h[e] = (f16)u[e];
+              l[e] = (f16)(u[e] - (float)h[e]);
+              x3bad |= x3_out_of_range(u[e]);
+            }
+            if (p.c_pair) {  // the lane's 8 columns sit in one 32-column chunk: hi at o, lo 32 halfs on
+              f16* o = p.C16 + x3_pair_index(row, col0, N, 0);
+              *reinterpret_cast<half8*>(o) = h;
+              *reinterpret_cast<half8*>(o + 32) = l;
+            } else {
+              *reinterpret_cast<half8*>(p.C16 + base) = h;
+              *reinterpret_cast<half8*>(p.C16 + p.c_lo + base) = l;
+            }
+          } else if (p.C16) {
+            half8 h;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) h[e] = (f16)v[e >> 2][e & 3];
+            *reinterpret_cast<half8*>(p.C16 + base) = h;
+          }
+          if (p.C32) {
+            *reinterpret_cast<float4*>(p.C32 + base) = make_float4(v[0][0], v[0][1], v[0][2], v[0][3]);
+            *reinterpret_cast<float4*>(p.C32 + base + 4) = make_float4(v[1][0], v[1][1], v[1][2], v[1][3]);
+          }
+        }
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
+    if (p.c_lo || p.c_pair) x3_raise(p.ovf, x3bad);
+    return;
+  }
   if (!p.R && p.C16 && !p.C32 && !p.c_lo) {
 #pragma unroll
     for (int ia = 0; ia < NIA; ++ia)
@@ -646,6 +754,13 @@ __device__ __forceinline__ void pp_epilogue(const GemmParams& p, floatx4 (&acc)[
 // MFMA section while its partner loads. ph3 waits vmcnt(6): everything but the three
 // pieces issued for tile t+2 has landed, i.e. all of tile t+1, read one phase later.
 // Same k order per output as every other tile, so results are bit-identical to them.
+// SP = 1: pass-major split operands (three K passes over planar planes). SP = 3: paired split
+// operands (GemmParams::a_pair / b_pair, [rows][2K]): a K tile is 32 of K, whose paired row -- the
+// chunk's 32 hi halfs, then its 32 lo halfs -- is byte for byte the f16 tile's 128-B row, so pieces,
+// swizzle, fragment reads and the barrier / vmcnt structure are the f16 loop's; af / bf index the
+// plane instead of the k half, and a phase runs the quadrant's three terms (lo.hi, hi.lo, hi.hi per
+// accumulator, gemm_glds_kernel SP = 3's order: same bits), 24 MFMAs between its barrier pair. How
+// tile 70256 serves paired operands under gemm_x3_pp 1 (launch_x3i).
 // DBG = 4 (probe build, tools/pp_trace.py): s_memtime at four points of every phase of the
 // first 12 K tiles, per wave, kept in spare LDS and dumped by one block into C32. DBG = 5
 // (probe): the epilogue computes everything but stores nothing.
@@ -653,6 +768,7 @@ template <int AM, int DBG = 0, int BM = 256, int ACT = -1, int SP = 0>
 __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmParams p) {
   static_assert(AM == A_PLAIN, "ping-pong tile: plain A only");
   static_assert(BM == 256 || BM == 128, "BM");
+  static_assert(SP == 0 || SP == 1 || (SP == 3 && BM == 256), "SP: pass-major, or paired on the 256-row tile");
   constexpr int BN = 256, BK = 64, WM = 2, WN = 4;
   constexpr int PA = BM / 2;            // rows per A piece (two wave rows x BM/4)
   constexpr int PB = 128;               // rows per B piece (four wave columns x 32)
@@ -678,6 +794,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmParams p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN, wn = wave - (wave / WN) * WN;
   const int M = p.M, N = p.N, K = p.K;
+  const int LDK = SP == 3 ? 2 * K : K;  // halfs per operand row in memory
   const int nbn = N / BN;
   const int nbm = (M + BM - 1) / BM;
   const int nwg = nbm * nbn;
@@ -701,23 +818,24 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmParams p) {
       const int pr = (wave * GA + i) * 8 + lrow;  // A-piece row
       const int m = m0 + (pr / (PA / 2)) * (BM / 2) + h * (BM / 4) + pr % (PA / 2);
       a_ok[h][i] = m < M;
-      a_src[h][i] = reinterpret_cast<const f16*>(p.A) + (size_t)(a_ok[h][i] ? m : 0) * K + sw<64>(pr, pchunk) * 8;
+      a_src[h][i] = reinterpret_cast<const f16*>(p.A) + (size_t)(a_ok[h][i] ? m : 0) * LDK + sw<64>(pr, pchunk) * 8;
     }
 #pragma unroll
     for (int i = 0; i < GB; ++i) {
       const int pr = (wave * GB + i) * 8 + lrow;  // B-piece row
       const int n = n0 + (pr >> 5) * 64 + h * 32 + (pr & 31);
-      b_src[h][i] = p.B + (size_t)n * K + sw<64>(pr, pchunk) * 8;
+      b_src[h][i] = p.B + (size_t)n * LDK + sw<64>(pr, pchunk) * 8;
     }
   }
   const f16* zero = reinterpret_cast<const f16*>(g_zero_page);
-  const int nk0 = K / BK;  // K tiles per pass (SP: three passes, as gemm_glds_kernel)
+  // K tiles per pass (SP = 1: three passes, as gemm_glds_kernel; SP = 3: a tile is 32 of K, 64 paired halfs)
+  const int nk0 = SP == 3 ? K / 32 : K / BK;
   // piece: 0 = A0, 1 = A1, 2 = B0, 3 = B1
   auto issue = [&](const int piece, const int kt) {
     f16* base = smem + (kt & 1) * BUF;
     int kk = kt;
     long long aoff = 0, boff = 0;
-    if constexpr (SP) {
+    if constexpr (SP == 1) {
       const int pl = (kt >= nk0) + (kt >= 2 * nk0);
       kk = kt - pl * nk0;
       aoff = pl == 0 ? p.a_lo : 0;
@@ -776,14 +894,25 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmParams p) {
     __builtin_amdgcn_sched_barrier(0);
     tmark();
     __builtin_amdgcn_s_setprio(1);
+    if constexpr (SP == 3) {  // the quadrant's three terms, term-major: each accumulator lo.hi, hi.lo, hi.hi
 #pragma unroll
-    for (int k = 0; k < 2; ++k)
+      for (int term = 0; term < 3; ++term)
 #pragma unroll
-      for (int i = 0; i < QI; ++i)
+        for (int i = 0; i < QI; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[qa * QI + i][qb * 2 + j] =
-              __builtin_amdgcn_mfma_f32_16x16x32_f16(bf[k][j], af[k][i], acc[qa * QI + i][qb * 2 + j], 0, 0, 0);
+          for (int j = 0; j < 2; ++j)
+            acc[qa * QI + i][qb * 2 + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
+                bf[term == 1][j], af[term == 0][i], acc[qa * QI + i][qb * 2 + j], 0, 0, 0);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 2; ++k)
+#pragma unroll
+        for (int i = 0; i < QI; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j)
+            acc[qa * QI + i][qb * 2 + j] =
+                __builtin_amdgcn_mfma_f32_16x16x32_f16(bf[k][j], af[k][i], acc[qa * QI + i][qb * 2 + j], 0, 0, 0);
+    }
     __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
     tmark();
@@ -791,7 +920,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmParams p) {
     __builtin_amdgcn_sched_barrier(0);
   };
 
-  const int nk = SP ? 3 * nk0 : nk0;
+  const int nk = SP == 1 ? 3 * nk0 : nk0;
   issue(0, 0);
   issue(3, 0);
   issue(1, 0);
@@ -856,7 +985,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmParams p) {
     if (s == 12345.678f) p.C32[0] = s;
     return;
   }
-  pp_epilogue<BM, DBG == 5, ACT>(p, acc, reinterpret_cast<char*>(smem), m0, n0, wm, wn, tid, lane);
+  pp_epilogue<BM, DBG == 5, ACT, SP == 3>(p, acc, reinterpret_cast<char*>(smem), m0, n0, wm, wn, tid, lane);
 }
 
 // BM=256 tiles: (BN, WM, WN, NS)
@@ -864,7 +993,19 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmParams p) {
 // K-interleaved split operands (16x16x32, 32-deep stages) in each A mode
 template <int BM, int BN, int WM, int WN, int NS, int BK>
 static int launch_x3i(const GemmParams& p, hipStream_t s, int nwg, dim3 blk) {
-  if (p.a_pair) {  // paired planes (launch_gemm: plain A, both operands paired, no split residual)
+  const int pp = opt().gemm_x3_pp;
+  if (BM == 256 && BN == 256 && NS == 2 && p.a_pair && (pp == 2 || (pp == 1 && p.act == ACT_NONE))) {
+    // tile 70256 on paired planes: the ping-pong schedule (same grid, same tile walk -- p.group_m is
+    // launch_cfg's gemm_glds_group_m --, same bits). gemm_x3_pp 1 gives it the launch classes whose median
+    // it lowered at B = 256 (profiles/x3_pp_gemm.txt, two runs): BERT's FFN2 by 9.5 / 8.7 % (not `clear` by
+    // the tool's rule: one slow ring round per run widens the ring arm's spread past the gain, though every
+    // ping-pong round is below every ring round), O-projection 4.3 / 4.1 % (clear), last-layer K|V 1.1 /
+    // 2.5 % (clear in one run). FFN1, the one class with an activation in its epilogue, was 2.3 / 1.3 %
+    // slower and stays on the ring: the activation is the dispatch's stand-in for that launch class, so a new
+    // paired launch class wants its own measurement. 2 runs every class on it (tests, A/B)
+    if constexpr (BM == 256 && BN == 256 && NS == 2)
+      hipLaunchKernelGGL((gemm_pp_kernel<A_PLAIN, 0, 256, -1, 3>), dim3(nwg), dim3(512), 0, s, p);
+  } else if (p.a_pair) {  // paired planes (launch_gemm: plain A, both operands paired, no split residual)
     hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, WM, WN, NS, A_PLAIN, 0, 16, BK, 0, -1, 3>), dim3(nwg), blk, 0, s, p);
   } else if (BM * BN <= 128 * 128 && opt().gemm_prefetch_r && p.amode == A_PLAIN && p.R && p.r_lo && p.K <= 512) {
     if constexpr (BM * BN <= 128 * 128)

@@ -191,6 +191,15 @@ struct Options {
   // fp32x3 fused QKV + attention (one head per workgroup): every other 256-block of workgroups issues its stage
   // refill after its first (1) or second (2) MFMA term group instead of right after the barrier (0); same bits
   int qkv_x3_late_dma = 0;
+  // K-interleaved split engine, tile 70256 on paired planes (GemmParams::a_pair): the ping-pong schedule
+  // (gemm_pp_kernel SP = 3: four phases per 32-deep K tile, tile t + 2 in flight under a counted vmcnt)
+  // instead of the two-stage ring (gemm_glds_kernel SP = 3). 0 = ring; 1 = ping-pong for the launches without
+  // an activation (BERT's FFN2, O-projection and last-layer K|V: faster by the median at B = 256, though of
+  // the three only the O-projection is `clear` by tools/bench_x3_pp.py's rule in both runs),
+  // the ring for FFN1 (slower by the median); 2 = ping-pong for every launch (tests, A/B). The activation
+  // stands in for the launch class: a new paired launch class should be measured before it relies on it. Any batch size; same bits. Planar
+  // operands and every other tile stay on the ring
+  int gemm_x3_pp = 1;
   // K-interleaved split engine, per launch class: forced tile (7xxxx), 0 = autotune. BERT FFN1 is
   // pinned to 70256 by default: it and the other tiles time within a few % of each other alone, so an
   // autotune would flip between them run to run, and the bench's roofline kernel (and its PMC traffic

@@ -126,6 +126,9 @@ SIGNATURES = {
                                ctypes.c_longlong, c_vp, c_int, c_int, c_int, c_int, c_vp]),
     'mec_gemm_f16x3_paired': (c_int, [c_vp, c_vp, ctypes.c_float, c_vp, c_vp, c_vp, c_int, ctypes.c_longlong, c_vp,
                                       c_int, c_int, c_int, c_int, c_vp]),
+    'mec_gemm_f16x3_paired_ln': (c_int, [c_vp, c_vp, ctypes.c_float, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int,
+                                         ctypes.c_longlong, ctypes.c_float, c_vp, c_int, c_int, c_int, c_int, c_vp,
+                                         c_vp]),
     'mec_conv_f16': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                              c_int, c_int, c_vp]),
     'mec_gemm_f32': (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp]),

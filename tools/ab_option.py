@@ -109,8 +109,9 @@ def main():
         np.savez(a.save, *[t.cpu().numpy() for t in base], x3_report=np.array(report))
     for v in a.values:
         d = [float((x - y).abs().max()) for x, y in zip(outs[v], base)]
-        print(json.dumps({'enc': a.enc, 'precision': a.precision, a.opt: v, 'ms': round(sorted(times[v])[len(times[v]) // 2], 4),
-                          'max_abs_diff_vs_first': d}))
+        t = sorted(times[v])
+        print(json.dumps({'enc': a.enc, 'precision': a.precision, a.opt: v, 'ms': round(t[len(t) // 2], 4),
+                          'min': round(t[0], 4), 'max': round(t[-1], 4), 'max_abs_diff_vs_first': d}))
 
 
 if __name__ == '__main__':
