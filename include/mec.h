@@ -465,6 +465,83 @@ int mec_image_canon_ragged_u8(const uint8_t* src, const int64_t* offs, const int
  * launches no such kernel (only L / LA images; every c_out 0) is not counted. */
 int mec_image_canon_prof_enable(int on);
 int mec_image_canon_prof_read(double* gray_ms, int* gray_count, double* canon_ms, int* canon_count);
+
+/* Baseline JPEG decoding of a ragged batch (csrc/jpeg.hip, csrc/jpeg_probe.h): what
+ *   Image.open(file).load()   with Pillow 12.2 on libjpeg-turbo (slow-integer IDCT, fancy upsampling)
+ * gives, byte for byte, for every file of the domain below; every other file stays with the host.
+ *
+ * mec_jpeg_probe: host only, needs no GPU, safe on arbitrary bytes (every read is bounds-checked). Returns 1 and
+ * fills *desc for a file the GPU decodes, 0 for a file the host decodes (*desc untouched), -1 for a null data or
+ * desc, seg_cap < 0, or segs null with seg_cap > 0. On the GPU iff all of: SOI; exactly one frame, SOF0, 8-bit;
+ * exactly one SOS naming all the frame's components in frame order with Ss = 0, Se = 63, Ah = Al = 0; only SOF0,
+ * DHT, DQT, DRI, APPn other than APP14 and COM segments before it (so no DNL, no Adobe segment, no arithmetic
+ * conditioning); one component sampled 1 x 1 (Pillow's L), or components 1, 2, 3 with chroma 1 x 1 and luma
+ * 1 x 1, 2 x 1 or 2 x 2 (Pillow's RGB through YCbCr); 8-bit quantization tables; Huffman table ids 0 or 1 whose
+ * counts give canonical codes that fit (as libjpeg requires); every table the scan names defined before SOS;
+ * mec_resize_on_gpu(H, W); W >= 5 where luma is sampled 2 x (narrower images take libjpeg-turbo's small-width
+ * paths, not restated); and entropy-coded data that splits into restart segments: with DRI = n > 0 exactly
+ * ceil(MCUs / n) of them, separated by RST0..RST7 in cyclic order, without DRI one; 0xFF00 is a stuffed byte; fill
+ * bytes 0xFF before a marker are skipped (before a stuffed zero they send the file to the host); the marker that
+ * ends the data is EOI. desc->nseg is the number of segments; where nseg <= seg_cap, segs[2 k] and
+ * segs[2 k + 1] take segment k's offset in the file and its length (markers and fill bytes excluded), otherwise
+ * segs is untouched: call again with room for nseg pairs.
+ *
+ * mec_jpeg_desc: H, W; ncomp 1 or 3; hs / vs the components' sampling factors; restart the interval in MCUs (0:
+ * none); nseg; qt[c] component c's quantization table, 64 values in zigzag order (as in the file); dc[c] / ac[c]
+ * its Huffman tables as the file's 16 counts and values (the library builds its decoding tables).
+ *
+ * mec_jpeg_workspace_bytes: the device workspace the batch needs (192 bytes per 8 x 8 block of every component,
+ * padded to whole MCUs: int16 coefficients, then u8 planes), or -1 for an inconsistent descriptor.
+ *
+ * mec_jpeg_decode_ragged: src (device, src_bytes long, any alignment) holds the files' bytes, or just their
+ * scans; segs (HOST, int64 pairs offset | length, image after image, sum of nseg pairs) places every segment in
+ * src. Image i is written as u8 [H_i, W_i, ncomp_i] at dst + dst_offs[i], the packed layout the calls above read
+ * as MEC_PIX_L / MEC_PIX_RGB. dst (device, 16-byte aligned, dst_bytes long; dst_offs multiples of 16) may lie in
+ * the allocation of src: a written range may overlap no segment, no other written range and not the workspace.
+ * ws (device, 16-byte aligned) is the workspace. status (device int32[B]) takes 0 for a decoded image, else one
+ * of the problems found in it, MEC_JPEG_ST_*: an invalid Huffman code; a DC category above 11; an AC size above 10;
+ * a coefficient index past 63; a segment that ends before its MCUs do; an IDCT intermediate outside int16 or a
+ * result outside [-512, 511] before range limiting; a DC or dequantized coefficient outside int16 (in the last
+ * two cases libjpeg-turbo's SIMD and C code differ, so Pillow's bytes would be a guess). Inside a segment the
+ * byte after an 0xFF is dropped, whatever it is. The bytes of an image with nonzero status are unspecified, but
+ * lie in its own range: no kernel reads outside the image's segments or writes outside its workspace and dst range,
+ * whatever the segments hold.
+ *
+ * descs, segs and dst_offs are HOST arrays. Everything is checked on the host before any launch: a null pointer,
+ * B < 0, B > 65535, a descriptor outside the domain above (sizes, components, sampling, restart and segment
+ * counts, table counts), a segment outside src_bytes, a misaligned or out-of-range dst_off, overlapping ranges
+ * and a short workspace return -1 with a message and launch nothing; B == 0 returns 0. The call uploads its
+ * descriptors and tables itself from a staging buffer it owns and re-uses once the previous call's kernels have
+ * finished: asynchronous on `stream`, NOT capturable in a graph. */
+typedef struct mec_jpeg_huff {
+  uint8_t counts[16];
+  uint8_t vals[256];
+} mec_jpeg_huff;
+typedef struct mec_jpeg_desc {
+  int32_t H, W, ncomp;
+  int32_t hs[3], vs[3];
+  int32_t restart, nseg;
+  uint16_t qt[3][64];
+  mec_jpeg_huff dc[3], ac[3];
+} mec_jpeg_desc;
+enum {
+  MEC_JPEG_ST_OK = 0,
+  MEC_JPEG_ST_BAD_CODE = 1,
+  MEC_JPEG_ST_DC_CATEGORY = 2,
+  MEC_JPEG_ST_AC_SIZE = 3,
+  MEC_JPEG_ST_COEF_INDEX = 4,
+  MEC_JPEG_ST_SEGMENT_END = 5,
+  MEC_JPEG_ST_IDCT_RANGE = 6,
+  MEC_JPEG_ST_COEF_RANGE = 7
+};
+int mec_jpeg_probe(const uint8_t* data, size_t n, mec_jpeg_desc* desc, int64_t* segs, int seg_cap);
+long long mec_jpeg_workspace_bytes(const mec_jpeg_desc* descs, int B);
+int mec_jpeg_decode_ragged(const uint8_t* src, size_t src_bytes, const mec_jpeg_desc* descs, const int64_t* segs,
+                           int B, uint8_t* dst, const int64_t* dst_offs, size_t dst_bytes, void* ws, size_t ws_bytes,
+                           int32_t* status, void* stream);
+/* hipEvent timing of the entropy, IDCT and upsample / colour kernels, process-wide, as mec_resize_prof_*. */
+int mec_jpeg_prof_enable(int on);
+int mec_jpeg_prof_read(double* entropy_ms, double* idct_ms, double* colour_ms, int* count);
 /* C[M,N] = act(A[M,K] . B[N,K]^T + bias (+ R)); f16 operands, fp32 accumulate.
  * act: 0 none, 1 relu, 2 gelu(erf). Any of bias/R/C16/C32 may be NULL (not both outputs). */
 /* Split-f16 GEMM (the MEC_PREC_FP32X3 engine): A and B each an f16 hi plane with its lo plane

@@ -85,6 +85,9 @@ enum KernelTag : int {
   TAG_CANON_GRAY = 22,  // image_canon.hip: the gray test and the conversion (mec_image_canon_prof_*)
   TAG_CANON_PIX = 23,
   TAG_AUDIO_LOAD = 24,  // audio_load.hip: decode + resample (mec_audio_load_prof_*)
+  TAG_JPEG_ENTROPY = 25,  // jpeg.hip: the three kernels of the JPEG decode (mec_jpeg_prof_*)
+  TAG_JPEG_IDCT = 26,
+  TAG_JPEG_COLOUR = 27,
 };
 
 // Tuning knobs (mec_set_option / mec_model_set_option, include/mec.h). Every model handle

@@ -19,18 +19,25 @@ RGBA or P inside that domain is uploaded in its native pixel format, and the RGB
 the channel selection run on the GPU as well (csrc/image_canon.hip, engine.ingest_ragged), again with 'host''s
 bytes; every other mode or size takes the path above.
 
+With decode='gpu' (opt-in, needs convert='gpu') the host does not decode either: a baseline JPEG file inside
+mec.jpeg.probe's domain is uploaded as its bytes and decoded on the GPU (csrc/jpeg.hip, engine.ingest_ragged_files)
+to Pillow's pixels, so the results equal decode='host''s bit for bit; every other file (PNG, progressive or CMYK
+JPEG, ...) and a file the kernels give up is decoded by Pillow as above. predict_files / extract_features_files
+take a batch of files at every setting.
+
 Added beyond the reference: predict_array(u8 image) and predict_batch(u8 [B,48,48]), and
 `backbone='mobilenet_v2'` (README.md:13 names MobileNetV2 as the image model; the reference
 code builds ResNet50): the same transform, head, feature and result dicts on a
 torchvision-mobilenet_v2 backbone (csrc/mobilenet.hip; parity unpinned, no reference code).
 """
 
+import io
 from typing import Dict
 
 import numpy as np
 
 from config import Config
-from mec import checkpoints, engine
+from mec import checkpoints, engine, jpeg as _jpeg
 from mec._lib import MecError
 from mec.image import MODEL_SHAPES, PIX_L, PIX_RGB, native_pixels, resize_on_gpu
 
@@ -86,7 +93,7 @@ _KINDS = {'resnet50': 'image', 'mobilenet_v2': 'image_mbv2'}
 
 class ImageInference:
     def __init__(self, weights=None, seed=None, device=None, backbone='resnet50', precision=None, resize='host',
-                 convert='host'):
+                 convert='host', decode='host'):
         if backbone not in _KINDS:
             raise ValueError(f'backbone must be one of {sorted(_KINDS)}')
         if resize not in ('host', 'gpu'):
@@ -95,6 +102,14 @@ class ImageInference:
             raise ValueError("convert must be 'host' or 'gpu'")
         if convert == 'gpu' and resize != 'gpu':
             raise ValueError("convert='gpu' requires resize='gpu'")
+        if decode not in ('host', 'gpu'):
+            raise ValueError("decode must be 'host' or 'gpu'")
+        if decode == 'gpu' and not (resize == 'gpu' and convert == 'gpu'):
+            raise ValueError("decode='gpu' requires resize='gpu' and convert='gpu'")
+        # 'gpu': a baseline JPEG file inside mec.jpeg.probe's domain is uploaded undecoded and decoded on the GPU
+        # (csrc/jpeg.hip) to Pillow's pixels, so with 'host''s results bit for bit; every other file is decoded by
+        # Pillow as with 'host'
+        self.decode = decode
         # 'gpu': an image of mode L, LA, RGB, RGBA or P inside the GPU resize's domain is uploaded as decoded; the
         # RGB conversion, the gray test and the channel selection run there too (csrc/image_canon.hip), with
         # 'host''s bytes and so with its results bit for bit
@@ -126,21 +141,27 @@ class ImageInference:
 
     def _device_parts(self, rows, pixels, ingest):
         """The device-made rows of a `forward_routed` list -> {model-input shape: (u8 batch on the device, its
-        rows, ascending)}. `pixels` are engine.ingest_ragged items. ingest True (the list holds a `Native`): one
-        engine.ingest_ragged call; False (L or RGB pixels only): one engine.resize_ragged call per channel count."""
+        rows, ascending)}, and the rows of the files the GPU decoder gave up. `pixels` are
+        engine.ingest_ragged_files items. ingest True (the list holds a `Native` or a file): one
+        engine.ingest_ragged_files call; False (L or RGB pixels only): one engine.resize_ragged call per channel
+        count."""
         if ingest:
-            _, groups = engine.ingest_ragged(pixels, self.device)
-            return {shape: (x, [rows[j] for j in local]) for shape, (x, local) in zip(MODEL_SHAPES, groups)}
+            _, groups, status = engine.ingest_ragged_files(pixels, self.device)
+            return ({shape: (x, [rows[j] for j in local]) for shape, (x, local) in zip(MODEL_SHAPES, groups)},
+                    [rows[j] for j in np.flatnonzero(status)])
         parts = {}
         for C in (1, 3):
             local = [j for j, px in enumerate(pixels) if px[0].shape[2] == C]
             if local:
                 parts[(224, 224, C)] = (engine.resize_ragged([pixels[j][0] for j in local], self.device),
                                         [rows[j] for j in local])
-        return parts
+        return parts, []
 
-    def forward_routed(self, items):
-        """items: a list of `route` results -> (feat [n,512], probs [n,7]) device tensors in the list's order.
+    def forward_routed(self, items, unreadable=None):
+        """items: a list of `route` results and undecoded files (mec.jpeg.Blob, decode='gpu') -> (feat [n,512],
+        probs [n,7]) device tensors in the list's order. A file the GPU decoder gives up is decoded by Pillow and
+        takes the host route; what Pillow raises for it is raised, or with a dict `unreadable` stored there by row
+        (that row's results are zero).
         One forward per model-input shape, (48,48,1) / (224,224,1) / (224,224,3), as a batch of PIL-resized
         images is grouped: the rows made on the device (`_device_parts`: `Native` items and `_route` results
         still to be resized) stand in their shape's batch where the host's results would, in ascending row order
@@ -152,13 +173,25 @@ class ImageInference:
         for row, it in enumerate(items):
             if isinstance(it, Native):
                 pixels.append(tuple(it))
+            elif isinstance(it, _jpeg.Blob):
+                pixels.append(it)
             elif it[1]:
                 pixels.append((it[0], PIX_L if it[0].shape[2] == 1 else PIX_RGB, None))
             else:
                 host[row] = it[0]
                 continue
             drows.append(row)
-        parts = self._device_parts(drows, pixels, any(isinstance(it, Native) for it in items))
+        parts, given_up = self._device_parts(drows, pixels, any(isinstance(it, (Native, _jpeg.Blob)) for it in items))
+        for row in given_up:
+            try:
+                host[row] = self._host_pixels(items[row].data)
+            except MecError:
+                raise
+            except Exception as e:
+                if unreadable is None:
+                    raise
+                unreadable[row] = e
+                host[row] = np.zeros((224, 224, 1), np.uint8)
         made = {row: (a.shape, False) for row, a in host.items()}
         made.update((row, (shape, True)) for shape, (_, prows) in parts.items() for row in prows)
         feat = torch.empty((len(items), 512), dtype=torch.float32, device=dev)
@@ -179,6 +212,13 @@ class ImageInference:
             feat.index_copy_(0, at(rows), f)
             probs.index_copy_(0, at(rows), p)
         return feat, probs
+
+    @staticmethod
+    def _host_pixels(data):
+        """A file's bytes -> the host-made model input, as resize='host' makes it (PIL's bytes are the GPU's)."""
+        from PIL import Image
+        with Image.open(io.BytesIO(data)) as im:
+            return _route(im, 'host')[0]
 
     def _convert_on_gpu(self) -> bool:
         return self.convert == 'gpu' and self.resize == 'gpu'
@@ -241,9 +281,67 @@ class ImageInference:
         """`extract_features_arrays`' probabilities as one result dict per image."""
         return [self._as_dict(self.emotions, p) for p in self.extract_features_arrays(arrays)[1]]
 
+    def file_item(self, path):
+        """An image file -> its `forward_routed` item; raises what Pillow raises for a file it cannot read. With
+        decode='gpu' the file is read once: a JPEG of the GPU decoder's domain goes on undecoded (mec.jpeg.probe),
+        every other file is opened by Pillow from the same bytes."""
+        from PIL import Image
+        if self.decode == 'gpu':
+            with open(path, 'rb') as f:
+                data = f.read()
+            blob = _jpeg.probe(data)
+            if blob is not None:
+                return blob
+            with Image.open(io.BytesIO(data)) as im:
+                return self.route(im)
+        with Image.open(path) as im:
+            return self.route(im)
+
+    def _forward_files(self, paths, unreadable):
+        """-> (feat [n,512], probs [n,7]) numpy; the rows Pillow cannot read are zero and stored in `unreadable`."""
+        items = []
+        for row, p in enumerate(paths):
+            try:
+                items.append(self.file_item(p))
+            except MecError:
+                raise
+            except Exception as e:
+                unreadable[row] = e
+                items.append((np.zeros((224, 224, 1), np.uint8), False))
+        if not items:
+            return np.zeros((0, 512), np.float32), np.zeros((0, 7), np.float32)
+        feat, probs = self.forward_routed(items, unreadable)
+        return feat.cpu().numpy(), probs.cpu().numpy()
+
+    def extract_features_files(self, paths):
+        """Image files -> (feat [n,512], probs [n,7]) numpy, each file treated as `extract_features` treats it,
+        the batch run as one forward per model-input shape; raises what Pillow raises for a file it cannot read.
+        With decode='gpu' the JPEG files of the GPU decoder's domain are uploaded undecoded in one copy and
+        decoded, converted and resized there."""
+        if self.model is None:
+            raise RuntimeError('image model not loaded')
+        unreadable = {}
+        feat, probs = self._forward_files(list(paths), unreadable)
+        for row in sorted(unreadable):
+            raise unreadable[row]
+        return feat, probs
+
+    def predict_files(self, paths):
+        """`predict` for a batch of files: one result dict per file, the fallback for a file Pillow cannot read."""
+        paths = list(paths)
+        if self.model is None:
+            return [self._fallback() for _ in paths]
+        unreadable = {}
+        probs = self._forward_files(paths, unreadable)[1]
+        for row in sorted(unreadable):
+            print(f"Image inference error: {unreadable[row]}")
+        return [self._fallback() if row in unreadable else self._as_dict(self.emotions, p) for row, p in enumerate(probs)]
+
     def predict(self, image_file_path: str) -> Dict:
         if self.model is None:
             return self._fallback()
+        if self.decode == 'gpu':
+            return self.predict_files([image_file_path])[0]
         try:
             from PIL import Image
             with Image.open(image_file_path) as im:
@@ -259,6 +357,9 @@ class ImageInference:
         """(512-d fc[2] feature, 7 probs) — one forward instead of three."""
         if self.model is None:
             return None, None
+        if self.decode == 'gpu':
+            feat, probs = self.extract_features_files([image_file_path])
+            return feat[0], probs[0]
         from PIL import Image
         with Image.open(image_file_path) as im:
             return self._forward_image(im)

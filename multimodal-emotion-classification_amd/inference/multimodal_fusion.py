@@ -34,7 +34,7 @@ _MODS = ('speech', 'text', 'image')
 
 class MultimodalFusion:
     def __init__(self, weights=None, seed=None, device=None, precision=None, image_resize='host',
-                 image_convert='host', audio_load='host'):
+                 image_convert='host', audio_load='host', image_decode='host'):
         weights = weights or {}
         self.emotions = Config.EMOTIONS
         self.weights = [0.3, 0.35, 0.35]  # speech, text, image (reference :23)
@@ -42,7 +42,7 @@ class MultimodalFusion:
         self.speech_inference = SpeechInference(weights.get('speech'), seed, device, load=audio_load)
         self.text_inference = TextInference(weights.get('text'), seed, device, precision=precision)
         self.image_inference = ImageInference(weights.get('image'), seed, device, precision=precision,
-                                              resize=image_resize, convert=image_convert)
+                                              resize=image_resize, convert=image_convert, decode=image_decode)
         w = checkpoints.resolve('fusion', weights.get('fusion'), seed)
         if w is not None:
             self.fusion_model = engine.FusionHead(w, device=device)  # raises MecError without HIP/GPU
@@ -166,7 +166,8 @@ class MultimodalFusion:
         # (audio_load='gpu': a PCM WAV file's bytes are read here and decoded on the GPU below; any other file
         # is decoded here, per file)
         audio = self.speech_inference.file_batch(bool(present[:, 0].any()))
-        images = []  # per compact image row: what ImageInference.route makes of the image
+        images = []  # per compact image row: what ImageInference.file_item makes of the file
+        image_req = []  # ... and its request
         ni = 0
         for b, (a, _, i) in enumerate(reqs):
             if a is not None:
@@ -178,9 +179,11 @@ class MultimodalFusion:
                     raise ValueError(f'request {b}: cannot read audio {a!r}: {e}') from e
             if i is not None:
                 try:
-                    from PIL import Image
-                    with Image.open(i) as im:
-                        images.append(self.image_inference.route(im))
+                    # image_decode='gpu': a JPEG file of the GPU decoder's domain is read here and decoded below
+                    images.append(self.image_inference.file_item(i))
+                    image_req.append(b)
+                except MecError:
+                    raise
                 except Exception as e:
                     raise ValueError(f'request {b}: cannot read image {i!r}: {e}') from e
                 ni += 1
@@ -202,7 +205,11 @@ class MultimodalFusion:
             # one forward per model-input shape, placed in compact order; with image_resize='gpu' the images
             # the GPU resizes are grouped by channel count and resized in one call per group; with
             # image_convert='gpu' they are converted and tested for gray there too
-            image = self.image_inference.forward_routed(images)
+            unreadable = {}  # a file the GPU decoder gave up and Pillow cannot read either
+            image = self.image_inference.forward_routed(images, unreadable)
+            for row in sorted(unreadable):
+                b = image_req[row]
+                raise ValueError(f'request {b}: cannot read image {reqs[b][2]!r}: {unreadable[row]}') from unreadable[row]
         # ---- one routed fusion call
         plan = engine.fusion_mixed_plan(present, self.fusion_model is not None, dev)
         if self.fusion_model is not None:

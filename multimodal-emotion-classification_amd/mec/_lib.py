@@ -63,6 +63,18 @@ class FusionMixedArgs(ctypes.Structure):
                 ('fused', c_vp), ('logits', c_vp), ('attn_w', c_vp), ('dec_w', c_vp)]
 
 
+class JpegHuff(ctypes.Structure):
+    """include/mec.h mec_jpeg_huff: a Huffman table as the file states it, 16 counts and the values."""
+    _fields_ = [('counts', ctypes.c_uint8 * 16), ('vals', ctypes.c_uint8 * 256)]
+
+
+class JpegDesc(ctypes.Structure):
+    """include/mec.h mec_jpeg_desc (mec_jpeg_probe's result, mec_jpeg_decode_ragged's input), field for field."""
+    _fields_ = [('H', ctypes.c_int32), ('W', ctypes.c_int32), ('ncomp', ctypes.c_int32),
+                ('hs', ctypes.c_int32 * 3), ('vs', ctypes.c_int32 * 3), ('restart', ctypes.c_int32),
+                ('nseg', ctypes.c_int32), ('qt', (ctypes.c_uint16 * 64) * 3), ('dc', JpegHuff * 3), ('ac', JpegHuff * 3)]
+
+
 # include/mec.h MEC_MOD_* (bits of a sample's `present`) and MEC_ROUTE_*
 MOD_SPEECH, MOD_TEXT, MOD_IMAGE = 1, 2, 4
 ROUTE_NONE, ROUTE_SINGLE, ROUTE_AVERAGE, ROUTE_ATTENTION = 0, 1, 2, 3
@@ -121,6 +133,12 @@ SIGNATURES = {
                                           ctypes.c_size_t, c_vp]),
     'mec_image_canon_prof_enable': (c_int, [c_int]),
     'mec_image_canon_prof_read': (c_int, [c_dp, ctypes.POINTER(c_int), c_dp, ctypes.POINTER(c_int)]),
+    'mec_jpeg_probe': (c_int, [c_vp, ctypes.c_size_t, ctypes.POINTER(JpegDesc), c_vp, c_int]),
+    'mec_jpeg_workspace_bytes': (ctypes.c_longlong, [c_vp, c_int]),
+    'mec_jpeg_decode_ragged': (c_int, [c_vp, ctypes.c_size_t, c_vp, c_vp, c_int, c_vp, c_vp, ctypes.c_size_t, c_vp,
+                                       ctypes.c_size_t, c_vp, c_vp]),
+    'mec_jpeg_prof_enable': (c_int, [c_int]),
+    'mec_jpeg_prof_read': (c_int, [c_dp, c_dp, c_dp, ctypes.POINTER(c_int)]),
     'mec_gemm_f16': (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp]),
     'mec_gemm_f16x3': (c_int, [c_vp, ctypes.c_longlong, c_vp, ctypes.c_longlong, ctypes.c_float, c_vp, c_vp, c_vp,
                                ctypes.c_longlong, c_vp, c_int, c_int, c_int, c_int, c_vp]),

@@ -13,7 +13,7 @@ import threading
 import numpy as np
 import torch
 
-from . import _lib, image as _image, synthetic, tokenize as _tok, wav as _wav
+from . import _lib, image as _image, jpeg as _jpeg, synthetic, tokenize as _tok, wav as _wav
 from ._lib import MecError
 
 TAG_BERT_FFN2 = 5  # launch class of BERT's FFN2 GEMM (mec_common.h Tag)
@@ -575,6 +575,47 @@ def _resize_on_device(lib, src, offs, hw, C, src_bytes, dev) -> torch.Tensor:
     return out
 
 
+def _jpeg_decode(lib, buf, src_bytes, blobs, scan_offs, dst_at, dst_offs, dst_bytes, status, dev):
+    """mec_jpeg_decode_ragged on `blobs` (mec.jpeg.Blob) whose scans lie at `scan_offs` of the device buffer `buf`
+    (src_bytes of it are sources): image k is written at buf + dst_at + dst_offs[k] (dst_bytes of room) and its
+    status into the device int32 tensor `status`. Allocates the workspace; `dev` is the current device."""
+    descs = _jpeg.desc_array([b.desc for b in blobs])
+    segs = np.ascontiguousarray(np.concatenate(
+        [b.segs + np.array([[int(o) - b.span[0], 0]], np.int64) for b, o in zip(blobs, scan_offs)]), np.int64)
+    ws_bytes = _jpeg.workspace_bytes([b.desc for b in blobs])
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    dst_offs = np.ascontiguousarray(dst_offs, np.int64)
+    _lib.check(lib.mec_jpeg_decode_ragged(_ptr(buf), src_bytes, ctypes.addressof(descs), segs.ctypes.data, len(blobs),
+                                          ctypes.c_void_p(buf.data_ptr() + dst_at), dst_offs.ctypes.data, dst_bytes,
+                                          _ptr(ws), ws_bytes, _ptr(status), _stream(dev)), 'mec_jpeg_decode_ragged')
+
+
+def decode_jpeg_ragged(blobs, device=None):
+    """A list of probed files (mec.jpeg.Blob) -> (images, status): images[k] is a device u8 tensor [H,W,C], C = 1
+    (Pillow's L) or 3 (RGB), holding what `Image.open(file).load()` gives, byte for byte; status is a device int32
+    tensor [B], 0 for a decoded image, else mec.jpeg.ST_* (the image's bytes are then unspecified: the caller
+    decodes that file on the host). The scans are packed into one pinned buffer and uploaded in one copy; the
+    images lie behind them in the same device buffer (mec_jpeg_decode_ragged; csrc/jpeg.hip). Asynchronous on the
+    current stream."""
+    lib = _lib.load()
+    dev = require_gpu(device)
+    B = len(blobs)
+    status = torch.zeros(B, dtype=torch.int32, device=dev)
+    if B == 0:
+        return [], status
+    scans = [b.scan() for b in blobs]
+    offs, _, end = _image.pack_layout([a.size for a in scans])
+    src_total = _image.pad16(end)
+    dst_offs, _, dst_end = _image.pack_layout([b.out_bytes for b in blobs])
+    room = _image.pad16(dst_end)
+    with torch.cuda.device(dev):
+        buf = torch.empty(src_total + room, dtype=torch.uint8, device=dev)
+        buf[:src_total].copy_(_pinned(src_total, zip(offs, scans)), non_blocking=True)
+        _jpeg_decode(lib, buf, src_total, blobs, offs, src_total, dst_offs, room, status, dev)
+    images = [buf[src_total + int(o):src_total + int(o) + b.out_bytes].view(b.H, b.W, b.C) for b, o in zip(blobs, dst_offs)]
+    return images, status
+
+
 def ingest_ragged(items, device=None):
     """A list of (u8 array, fmt, palette or None) -- images in their native pixel formats, fmt one of
     mec.image.PIX_* ([H,W] or [H,W,bpp]; a PIX_P image with its palette, u8 [768]) -> (gray, groups): gray is a
@@ -590,12 +631,32 @@ def ingest_ragged(items, device=None):
     mec_image_canon_ragged_u8 converts the images whose native bytes are not what their consumer reads, and one
     mec_resize_ragged_u8 call per channel count reads untouched and converted images from the same buffer. Every
     image must lie in mec.image.resize_on_gpu's domain (ValueError otherwise)."""
+    gray, groups, _ = ingest_ragged_files(items, device)
+    return gray, groups
+
+
+def ingest_ragged_files(items, device=None):
+    """`ingest_ragged` for a batch that mixes its items with undecoded JPEG files (mec.jpeg.Blob, what
+    mec.jpeg.probe returns for a file of the GPU decoder's domain) -> (gray, groups, status). A file's scan goes up
+    in the same single copy as the other items' pixels; mec_jpeg_decode_ragged decodes the files into room behind
+    the sources, where the gray test, the conversion and the resize read them as PIX_L / PIX_RGB images like any
+    other. status is an int32 array [B]: 0 for every item but a file the kernels gave up (mec.jpeg.ST_*), which is
+    in no group and whose gray flag means nothing: the caller decodes it on the host. The statuses are read back
+    with the gray flags, in the call's one synchronisation."""
     lib = _lib.load()
     dev = require_gpu(device)
     B = len(items)
-    arrs = [_image.check_image(i, a, fmt=fmt, pal=pal) for i, (a, fmt, pal) in enumerate(items)]
-    pals = []
-    for i, (_, _, pal) in enumerate(items):
+    isblob = [isinstance(it, _jpeg.Blob) for it in items]
+    arrs, pals = [], []
+    for i, it in enumerate(items):
+        if isblob[i]:
+            if not _image.resize_on_gpu(it.H, it.W):
+                raise ValueError(f'image {i}: {it.H} x {it.W} is outside the GPU resize\'s domain')
+            arrs.append(it.scan())
+            pals.append(None)
+            continue
+        a, fmt, pal = it
+        arrs.append(_image.check_image(i, a, fmt=fmt, pal=pal))
         if pal is not None:
             pal = np.ascontiguousarray(pal, np.uint8).reshape(-1)
             if pal.size != _image.PAL_BYTES:
@@ -603,41 +664,69 @@ def ingest_ragged(items, device=None):
             pal = pal.tobytes()
         pals.append(pal)
     if B == 0:
-        return np.zeros(0, bool), [(torch.empty((0,) + s, dtype=torch.uint8, device=dev), []) for s in _image.MODEL_SHAPES]
-    fmts = np.array([fmt for _, fmt, _ in items], np.int32)
-    hw = np.array([a.shape[:2] for a in arrs], np.int32).reshape(B, 2)
-    offs, pal_at, end = _image.pack_layout([a.size for a in arrs], [p for p in pals if p is not None])
+        return (np.zeros(0, bool), [(torch.empty((0,) + s, dtype=torch.uint8, device=dev), []) for s in _image.MODEL_SHAPES],
+                np.zeros(0, np.int32))
+    fmts = np.array([it.fmt if b else it[1] for it, b in zip(items, isblob)], np.int32)
+    hw = np.array([(it.H, it.W) if b else a.shape[:2] for it, b, a in zip(items, isblob, arrs)], np.int32).reshape(B, 2)
+    up_offs, pal_at, end = _image.pack_layout([a.size for a in arrs], [p for p in pals if p is not None])
     pal_off = np.array([-1 if p is None else pal_at[p] for p in pals], np.int64)
     src_total = _image.pad16(end)
+    # the decoded files follow the sources; from there on they are images like the others
+    blob_at = np.array([i for i in range(B) if isblob[i]], np.int64)
+    blobs = [items[i] for i in blob_at]
+    dec_offs, _, dec_end = _image.pack_layout([b.out_bytes for b in blobs])
+    dec_total = src_total + _image.pad16(dec_end)
+    offs = up_offs.copy()
+    offs[blob_at] = src_total + dec_offs
     cap = sum(_image.canon_room(f, H, W) for f, (H, W) in zip(fmts, hw.tolist()))  # the most the converted images take
-    total = src_total + cap
-    stage = _pinned(src_total, list(zip(offs, arrs)) + [(o, np.frombuffer(p, np.uint8)) for p, o in pal_at.items()])
+    total = dec_total + cap
+    stage = _pinned(src_total, list(zip(up_offs, arrs)) + [(o, np.frombuffer(p, np.uint8)) for p, o in pal_at.items()])
     with torch.cuda.device(dev):
         stream = _stream(dev)
         buf = torch.empty(total, dtype=torch.uint8, device=dev)
         buf[:src_total].copy_(stage, non_blocking=True)
-        gray_d = torch.empty(B, dtype=torch.int32, device=dev)
+        flags_d = torch.empty(B + len(blobs), dtype=torch.int32, device=dev)  # the gray flags, then the files' statuses
+        if blobs:
+            _jpeg_decode(lib, buf, src_total, blobs, up_offs[blob_at], src_total, dec_offs, dec_total - src_total,
+                         flags_d[B:], dev)
         _lib.check(lib.mec_image_gray_ragged_u8(_ptr(buf), offs.ctypes.data, hw.ctypes.data, fmts.ctypes.data,
-                                                pal_off.ctypes.data, B, src_total, _ptr(gray_d), stream),
+                                                pal_off.ctypes.data, B, dec_total, _ptr(flags_d), stream),
                    'mec_image_gray_ragged_u8')
-        gray_h = torch.empty(B, dtype=torch.int32, pin_memory=True)
-        gray_h.copy_(gray_d, non_blocking=True)
+        flags_h = torch.empty(B + len(blobs), dtype=torch.int32, pin_memory=True)
+        flags_h.copy_(flags_d, non_blocking=True)
         torch.cuda.current_stream(dev).synchronize()
-        gray = gray_h.numpy().astype(bool)
-        face, chan, c_out, dst_offs, read_at = _image.canon_plan(gray, hw, fmts, offs, src_total)
+        gray = flags_h.numpy()[:B].astype(bool)
+        status = np.zeros(B, np.int32)
+        status[blob_at] = flags_h.numpy()[B:]
+        ok = np.flatnonzero(status == 0)  # a file the kernels gave up is no image from here on
+        offs, hw, fmts, pal_off = (np.ascontiguousarray(a[ok]) for a in (offs, hw, fmts, pal_off))
+        face, chan, c_out, dst_offs, read_at = _image.canon_plan(gray[ok], hw, fmts, offs, dec_total)
         if c_out.any():
             _lib.check(lib.mec_image_canon_ragged_u8(
-                _ptr(buf), offs.ctypes.data, hw.ctypes.data, fmts.ctypes.data, pal_off.ctypes.data, c_out.ctypes.data,
-                dst_offs.ctypes.data, B, src_total, ctypes.c_void_p(buf.data_ptr() + src_total), cap, stream),
-                'mec_image_canon_ragged_u8')
+                _ptr(buf), offs.ctypes.data, hw.ctypes.data, fmts.ctypes.data, pal_off.ctypes.data,
+                c_out.ctypes.data, dst_offs.ctypes.data, len(ok), dec_total, ctypes.c_void_p(buf.data_ptr() + dec_total),
+                cap, stream), 'mec_image_canon_ragged_u8')
         n48 = int(face.sum())
-        groups = [(buf[src_total:src_total + n48 * 2304].view(n48, 48, 48, 1), [int(i) for i in np.flatnonzero(face)])]
+        groups = [(buf[dec_total:dec_total + n48 * 2304].view(n48, 48, 48, 1), [int(i) for i in ok[np.flatnonzero(face)]])]
         for C in (1, 3):
             rows = np.flatnonzero(~face & (chan == C))
             out = _resize_on_device(lib, buf, np.ascontiguousarray(read_at[rows]), np.ascontiguousarray(hw[rows]), C,
                                     total, dev)
-            groups.append((out, [int(i) for i in rows]))
-    return gray, groups
+            groups.append((out, [int(i) for i in ok[rows]]))
+    return gray, groups, status
+
+
+def jpeg_prof(on: bool):
+    """Switch the hipEvent timing of the JPEG decode's three kernels on or off (process-wide)."""
+    _lib.check(_lib.load().mec_jpeg_prof_enable(int(bool(on))), 'mec_jpeg_prof_enable')
+
+
+def jpeg_prof_read():
+    """(entropy ms, IDCT ms, upsample / colour ms, calls) since the last read or enable; synchronizes on the events."""
+    e, i, c, n = ctypes.c_double(), ctypes.c_double(), ctypes.c_double(), ctypes.c_int()
+    _lib.check(_lib.load().mec_jpeg_prof_read(ctypes.byref(e), ctypes.byref(i), ctypes.byref(c), ctypes.byref(n)),
+               'mec_jpeg_prof_read')
+    return e.value, i.value, c.value, n.value
 
 
 def canon_prof(on: bool):

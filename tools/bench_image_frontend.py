@@ -20,6 +20,13 @@ convert='gpu' setting: engine.ingest_ragged alone on the host clock (pack, one c
 read-back, the conversion kernel, the resizes), and the gray and conversion kernels' device-event times
 (mec_image_canon_prof_*) with their bytes: the gray kernel reads the RGB / RGBA / P images, the conversion kernel
 reads the images it converts and writes H W c_out for each.
+
+The decode comparison (--decode-kinds) goes from files to probabilities, ImageInference.predict_files with decode='gpu'
+against decode='host' (both with resize='gpu' and convert='gpu') alternating in the same run: 'jpeg_420' is --batch
+480 x 640 4:2:0 quality-75 JPEG files of smooth-plus-noise synthetic content, 'jpeg_face' --batch 48 x 48 gray
+JPEG files, all made by Pillow at run time in a temporary directory. Also reported: the file bytes, the restart
+segments (one wave each in the entropy kernel), engine.decode_jpeg_ragged alone on the host clock and the three
+kernels' device-event times per call (mec_jpeg_prof_*).
 Prints one JSON line; --out also writes it to a file.
 """
 import argparse
@@ -27,6 +34,7 @@ import json
 import os
 import statistics
 import sys
+import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -149,6 +157,74 @@ def canon_events(inf, images, device, iters):
     return out
 
 
+DECODE_KINDS = ('jpeg_420', 'jpeg_face')
+
+
+def make_files(kind, B, rng, folder):
+    """B JPEG files made by Pillow: smooth content (a few sinusoids per channel) plus noise."""
+    from PIL import Image
+    H, W = (480, 640) if kind == 'jpeg_420' else (48, 48)
+    C = 3 if kind == 'jpeg_420' else 1
+    yy, xx = np.mgrid[0:H, 0:W].astype(np.float32)
+    paths = []
+    for i in range(B):
+        a = np.zeros((H, W, C), np.float32)
+        for c in range(C):
+            fy, fx, ph = rng.uniform(0.5, 4, 2), rng.uniform(0.5, 4, 2), rng.uniform(0, 6.28, 2)
+            a[..., c] = 128 + 50 * np.sin(fy[0] * yy / H * 6.28 + ph[0]) * np.cos(fx[0] * xx / W * 6.28) \
+                + 40 * np.sin(fx[1] * xx / W * 6.28 + fy[1] * yy / H * 6.28 + ph[1])
+        a = np.clip(a + rng.normal(0, 6, a.shape), 0, 255).astype(np.uint8)
+        paths.append(os.path.join(folder, f'{kind}_{i}.jpg'))
+        if C == 3:
+            Image.fromarray(a, 'RGB').save(paths[-1], quality=75, subsampling=2)
+        else:
+            Image.fromarray(a[..., 0], 'L').save(paths[-1], quality=75)
+    return paths
+
+
+def decode_bench(inf, kind, a, dev, rng):
+    from mec import jpeg as mjpeg
+    B = a.batch
+    with tempfile.TemporaryDirectory() as folder:
+        paths = make_files(kind, B, rng, folder)
+        inf.resize, inf.convert = 'gpu', 'gpu'
+
+        def predict(decode):
+            inf.decode = decode
+            return inf.predict_files(paths)
+
+        fns = {k: (lambda k=k: predict(k)) for k in ('host', 'gpu')}
+        for _ in range(a.warmup):
+            got = {k: fn() for k, fn in fns.items()}
+        assert got['host'] == got['gpu'], f'{kind}: the settings disagree'
+        med = windows(fns, a.windows, a.repeats, dev)
+        blobs = []
+        for p in paths:
+            with open(p, 'rb') as f:
+                blobs.append(mjpeg.probe(f.read()))
+        inf.decode = 'host'
+    assert all(b is not None for b in blobs), f'{kind}: a file is outside the GPU decoder\'s domain'
+    for _ in range(3):
+        _, status = engine.decode_jpeg_ragged(blobs, dev)
+    assert not status.cpu().numpy().any()
+    host_ms = [clock(lambda: engine.decode_jpeg_ragged(blobs, dev), dev)[0] for _ in range(a.event_iters)]
+    engine.jpeg_prof(True)
+    for _ in range(a.event_iters):
+        engine.decode_jpeg_ragged(blobs, dev)
+    torch.cuda.synchronize(dev)
+    e_ms, i_ms, c_ms, n = engine.jpeg_prof_read()
+    engine.jpeg_prof(False)
+    assert n == a.event_iters
+    out_bytes = sum(b.out_bytes for b in blobs)
+    ws = mjpeg.workspace_bytes([b.desc for b in blobs])
+    return {'files': B, 'file_bytes': sum(len(b.data) for b in blobs), 'scan_bytes': sum(b.span[1] - b.span[0] for b in blobs),
+            'restart_segments': sum(len(b.segs) for b in blobs), 'decoded_bytes': out_bytes, 'workspace_bytes': ws,
+            'files_to_probabilities': {k: summary(med[k], B) for k in med},
+            'gpu_over_host_speedup': statistics.median(med['host']) / statistics.median(med['gpu']),
+            'decode_jpeg_ragged_host_clock_ms': {'median': statistics.median(host_ms), 'min_max': [min(host_ms), max(host_ms)]},
+            'kernels_ms_per_call': {'iters': n, 'entropy': e_ms / n, 'idct': i_ms / n, 'colour': c_ms / n}}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('--batch', type=int, default=256)
@@ -157,6 +233,7 @@ def main():
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--event-iters', type=int, default=20)
     ap.add_argument('--kinds', default=','.join(KINDS), help='comma-separated workloads')
+    ap.add_argument('--decode-kinds', default=','.join(DECODE_KINDS), help='comma-separated file workloads (may be empty)')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -178,7 +255,7 @@ def main():
         return [inf._as_dict(inf.emotions, p) for p in probs]
 
     rng = np.random.default_rng(0)
-    for kind in a.kinds.split(','):
+    for kind in [k for k in a.kinds.split(',') if k]:
         images = make_images(kind, B, rng)
         fns = {k: (lambda k=k: predict(k, images)) for k in SETTINGS}
         for _ in range(a.warmup):
@@ -197,6 +274,8 @@ def main():
                      'convert_gpu': canon_events(inf, images, dev, a.event_iters),
                      'resize_only_rgb_images': {'images': len(rgb), **{k: summary(parts[k], len(rgb)) for k in parts}},
                      'kernels_rgb_images': kernel_events(rgb, dev, a.event_iters) if rgb else None}
+    for kind in [k for k in a.decode_kinds.split(',') if k]:
+        res[kind] = decode_bench(inf, kind, a, dev, rng)
     print(json.dumps(res))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
